@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Throughput benchmark of the PointsToWood inference hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision f16x3|fp16|bf16|fp32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision f16x3|fp16|bf16|fp32] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (``metric``, ``value``, ``ms_per_step``, ...).
+``--full`` adds everything else the benchmark measures, described below: the PCIe-inclusive and ``single_call`` regions,
+the profiled step (``roofline``, ``search``, ``hbm_kernels``, per-kernel times, level sizes), the extra ``workloads`` and
+the CPU baseline.  ``--dump-outputs DIR`` writes the logits of the last timed step as ``DIR/logits.npy`` (float32; rank
+order under ``--gpus N``); the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 One "step" = one pass of the hot path (``Net.forward``: geometry + features, reference
 ``pointstowood/src/model.py:226-245``) over one voxel batch of BASELINE.json ``configs[1]``:
@@ -83,7 +89,37 @@ def parse_args(argv=None):
                          "MFMA per product (the reference's autocast arithmetic; outside the 1e-4 bar); fp32: fp32 MFMA")
     ap.add_argument("--engine-opt", action="append", default=[], metavar="KEY=VALUE",
                     help="EngineOptions field for the benched Net (A/B runs), e.g. --engine-opt res_streams=2 --engine-opt sampler=sort")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline line: PCIe-inclusive and single_call regions, the profiled step (roofline, search, "
+                         "hbm_kernels, per-kernel times), the extra workloads and the CPU baseline (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT = 64 << 20   # --dump-outputs: bytes written in all
+
+
+def dump_outputs(path, arrays, seed=0):
+    """--dump-outputs: every tensor of ``arrays`` as ``path/<name>.npy`` (float64 stays float64, the rest become float32).  Over
+    DUMP_LIMIT bytes in all, every array is cut to the same fixed, seeded sample of rows (the arrays must have one length),
+    whose indices go to ``path/rows.npy`` (as float64: exact)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        out[name] = (t if t.dtype == torch.float64 else t.float()).numpy()
+    room = DUMP_LIMIT - 4096   # (the .npy headers)
+    if sum(a.nbytes for a in out.values()) > room:
+        (n,) = {a.shape[0] for a in out.values()}
+        row_bytes = sum(a.nbytes // n for a in out.values()) + 8
+        rows = np.sort(np.random.default_rng(seed).choice(n, room // row_bytes, replace=False))
+        out = {name: a[rows] for name, a in out.items()}
+        out["rows"] = rows.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def engine_options(pairs):
@@ -564,7 +600,7 @@ def plot_main(args, world, rank, device, dist):
     side = max(10.0, 100.0 * (n / 10_000_000) ** 0.5)
     pc = forest_plot(n, side=side).to(device)
     gen = lambda: torch.Generator(device=device).manual_seed(0)
-    steps, warm = max(1, min(args.steps, 3)), max(1, min(args.warmup, 1))
+    steps, warm = args.steps, args.warmup
     for _ in range(warm):
         segment_plot(pc, net, generator=gen(), dist=dist)
     times, stats = [], {}
@@ -587,6 +623,8 @@ def plot_main(args, world, rank, device, dist):
             dt = float(t)
         times.append(dt)
     assert bool(torch.isfinite(pwood).all())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"n_z": n_z, "label": label, "pwood": pwood})
     if rank == 0:
         dt = sum(times) / len(times)
         print(json.dumps({
@@ -605,6 +643,30 @@ def plot_main(args, world, rank, device, dist):
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def timing_note(args, dt):
+    return (f"timed region {dt:.2f} s ({args.steps} steps) right after {args.warmup} warm-up steps: a cold-clock number; box-to-box spread of this "
+            "line is +-3-5 % (DVFS), same-box A/Bs are in docs/LAB_NOTES.md")
+
+
+def headline(args, world, nb, dt, per_step, net, sizes=None):
+    """The contract keys of the voxel-batch line, in their order; ``sizes`` (level sizes of batch 0) comes from --full's
+    profiled step."""
+    config = {"workload": "BASELINE configs[1]: batch_size 8 x 16384-pt 2 m voxels, k=32, xyz-only, 1 batch per GPU per step, "
+                          f"{nb} distinct seeded batches in rotation, inputs resident in HBM",
+              "global_batch_voxels": world * BATCH, "points_per_step": world * BATCH * NPTS, "C": C}
+    if sizes is not None:
+        config["level_sizes_batch0"] = sizes
+    config.update({"parallelism": f"voxel-batch sharding x{world}, RCCL all-gather of logits "
+                                  + ("once after the last step" if args.gather == "final" else "after every step"),
+                   "pipeline": ("HIP streams: geometry(i+1) || features(i), features alternating over "
+                                f"{net.engine_options.feature_streams} high-priority streams") if args.pipeline else "sequential"})
+    return {"metric": "classified points/sec", "value": world * args.steps * BATCH * NPTS / dt, "unit": "points/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+            "ms_per_step_median": statistics.median(per_step),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
+            "config": config}
 
 
 def main():
@@ -647,8 +709,9 @@ def main():
     nb = max(1, args.batches)
     host = [host_batch(rank, j) for j in range(nb)]
     resident = [Feed.to_device(b, device) for b in host]
-    pinned = [{k: b[k].pin_memory() for k in Feed.FIELDS} for b in host]
-    out_host = [torch.empty(BATCH * NPTS, dtype=torch.float32).pin_memory() for _ in range(nb)]
+    if args.full and not args.no_pcie:   # the PCIe-inclusive region's host side
+        pinned = [{k: b[k].pin_memory() for k in Feed.FIELDS} for b in host]
+        out_host = [torch.empty(BATCH * NPTS, dtype=torch.float32).pin_memory() for _ in range(nb)]
     peak = PEAK_TFLOPS[args.precision]
 
     gather_marks = []
@@ -743,6 +806,23 @@ def main():
     run(args.warmup)
     dt, per_step, out, rank_stats = timed(args.steps, False)
     assert bool(torch.isfinite(out).all())
+    if rank == 0 and args.dump_outputs:
+        # --gather final hands back every step of every rank, rank-major: keep the last step of each
+        last = out.reshape(world, args.steps, -1)[:, -1] if world > 1 and args.gather == "final" else out
+        dump_outputs(args.dump_outputs, {"logits": last.reshape(-1)})
+
+    if not args.full:
+        if rank == 0:
+            line = {"timing_note": timing_note(args, dt), "range_fallbacks": int(getattr(net._engine, "range_fallbacks", 0))}
+            if rank_stats is not None:
+                line["ranks"] = rank_stats
+            line.update(headline(args, world, nb, dt, per_step, net))
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     pcie = None
     if not args.no_pcie:
         run(min(2, args.warmup), pcie=True)
@@ -776,7 +856,6 @@ def main():
         dom_ms, dom_launches = per[dom]
         achieved = 2.0 * kmacs[dom] / (dom_ms * 1e-3) / 1e12
         saved = hoist_saved_macs(geo, net.engine_options) if dom == "gemm_kernel" else 0
-        pts = world * args.steps * BATCH * NPTS
         h = args.precision != "fp32"
         kname = {"gemm_kernel": (f"gemm_hp_kernel<{args.precision}> (persistent; 256x256, 128x128 and 64x128 tile instantiations, split-K tails, all launches)"
                                  if h else "gemm_kernel"),
@@ -843,8 +922,7 @@ def main():
             "search": search,
             "hbm_kernels": hbm,
             "kernel_ms_per_step": {kname: round(v[0], 4) for kname, v in sorted(per.items(), key=lambda kv: -kv[1][0])},
-            "timing_note": f"timed region {dt:.2f} s ({args.steps} steps) right after {args.warmup} warm-up steps: a cold-clock number; box-to-box spread of this "
-                           "line is +-3-5 % (DVFS), same-box A/Bs are in docs/LAB_NOTES.md",
+            "timing_note": timing_note(args, dt),
             # forwards the f16x3 range guard recomputed on the fp32 MFMA path (0 on this benchmark: a non-zero count would mean the
             # timed steps were not f16x3 steps)
             "range_fallbacks": int(getattr(net._engine, "range_fallbacks", 0)),
@@ -852,18 +930,8 @@ def main():
         })
         if rank_stats is not None:
             line["ranks"] = rank_stats
+        line.update(headline(args, world, nb, dt, per_step, net, sizes))
         line.update({
-            "metric": "classified points/sec", "value": pts / dt, "unit": "points/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            "ms_per_step_median": statistics.median(per_step),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
-            "config": {"workload": "BASELINE configs[1]: batch_size 8 x 16384-pt 2 m voxels, k=32, xyz-only, 1 batch per GPU per step, "
-                                   f"{nb} distinct seeded batches in rotation, inputs resident in HBM",
-                       "global_batch_voxels": world * BATCH, "points_per_step": world * BATCH * NPTS, "C": C,
-                       "level_sizes_batch0": sizes, "parallelism": f"voxel-batch sharding x{world}, RCCL all-gather of logits "
-                                                                    + ("once after the last step" if args.gather == "final" else "after every step"),
-                       "pipeline": ("HIP streams: geometry(i+1) || features(i), features alternating over "
-                                    f"{net.engine_options.feature_streams} high-priority streams") if args.pipeline else "sequential"},
             "roofline": {"bound": "mfma", "kernel": kname.get(dom, dom), "achieved": achieved, "peak": peak,
                          "unit": "TFLOP/s", "frac": achieved / peak, "traffic": traffic, "traffic_unit": "bytes per launch (FETCH_SIZE x2 + WRITE_SIZE)",
                          "traffic_bytes_per_step": traffic_step, "traffic_source": traffic_src, "note": notes[args.precision],

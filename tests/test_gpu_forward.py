@@ -438,13 +438,13 @@ def test_voxeliser_on_gpu_matches_cpu_restatement():
 
 
 def test_bench_contract_line():
-    """bench.py prints ONE JSON line with the contract's keys (driver contract + roofline + cpu_baseline objects)."""
+    """bench.py --full prints ONE JSON line with the contract's keys (driver contract + roofline + cpu_baseline objects)."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, env=dict(os.environ, P2W_BENCH_WATCHDOG="300"))
     assert r.returncode == 0, r.stderr[-6000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -467,6 +467,34 @@ def test_bench_contract_line():
     assert keys.index("workloads") < keys.index("metric") < keys.index("roofline") < keys.index("single_call") < keys.index("pcie_inclusive")
     assert keys[-1] == "pcie_inclusive" and d["single_call"]["ms_per_step"] > 0 and d["pcie_inclusive"]["ms_per_step"] > 0
     assert "error" not in d["workloads"]
+
+
+def test_bench_plain_line_and_outputs(tmp_path):
+    """A plain bench.py run prints ONE JSON line with the headline keys and nothing of --full; --dump-outputs writes the last
+    timed step's logits, and a second run on the same arguments writes the same bits."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = []
+    for i in range(2):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / str(i))],
+                           capture_output=True, text=True, timeout=300, env=dict(os.environ, P2W_BENCH_WATCHDOG="240"))
+        assert r.returncode == 0, r.stderr[-6000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["metric"] == "classified points/sec" and d["unit"] == "points/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f16x3" and d["steps"] == 5 and d["warmup"] == 1 and d["ms_per_step"] > 0
+        assert abs(d["value"] - 8 * 16384 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+        for key in ("roofline", "workloads", "cpu_baseline", "single_call", "pcie_inclusive", "search", "kernel_ms_per_step"):
+            assert key not in d, key
+        assert sorted(os.listdir(tmp_path / str(i))) == ["logits.npy"]
+        outs.append(np.load(tmp_path / str(i) / "logits.npy"))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (8 * 16384,) and np.isfinite(outs[0]).all()
+    assert np.array_equal(outs[0], outs[1])
 
 
 # ---- INTEGRATION.md route B as a composition: the reference forward's statements over pointstowood_amd.ops -----------------

@@ -7,6 +7,7 @@ rounds=${1:-3}; shift
 for r in $(seq 1 $rounds); do
   for t in . ab_old; do
     extra=""; grep -q -- "--no-workloads" $t/bench.py && extra="--no-workloads"
+    grep -q -- '"--full"' $t/bench.py && extra="$extra --full"      # (a tree from before --full runs all of it by default)
     (cd $t && python bench.py --no-cpu-baseline --no-pcie $extra --steps 24 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['kernel_ms_per_step']

@@ -4,7 +4,7 @@ set -u
 export TMPDIR=/tmp TAG=${TAG:-r6}
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/prof_${TAG}_f16x3
 mkdir -p $OUT; rm -rf $OUT/mfma
-CMD="$ROOT/bench.py --no-cpu-baseline --no-pcie --no-single-call --no-workloads --steps 10 --warmup 2 --precision f16x3 --pipeline 0 --engine-opt overlap=0 --engine-opt single_res_streams=1"
+CMD="$ROOT/bench.py --full --no-cpu-baseline --no-pcie --no-single-call --no-workloads --steps 10 --warmup 2 --precision f16x3 --pipeline 0 --engine-opt overlap=0 --engine-opt single_res_streams=1"
 cd /tmp
 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $OUT/mfma -- python3 $CMD > $OUT/mfma.json 2> $OUT/mfma.err
 cd $ROOT
