@@ -242,6 +242,31 @@ int32_t p2w_knn_refine_f64(const double* cand_sorted, const int32_t* cand_index,
                            double oz, const double* q, int32_t m, int32_t nc, int32_t k, int32_t* nbr, int32_t* deg,
                            p2w_stream_t stream);
 
+/* Euclidean clustering - EuclideanCluster.cluster (pointstowood/src/euclidean_clustering.py:13-47): points i and j are joined when
+ * their float64 distance is within `tolerance` (cKDTree.query_ball_point(points[i], tolerance), p = 2: here
+ * ((dx*dx + dy*dy) + dz*dz) <= tolerance*tolerance, every operation rounded on its own); a cluster is a connected component; the
+ * components with min_size <= size <= max_size are numbered 0, 1, ... in ascending order of their smallest point index (the order
+ * the reference's seed loop meets them), every other point gets -1.
+ * In : the points in the cell-sorted order of a p2w_voxel_sample call over their fp32 coordinates made local to the cloud's minimum:
+ *      xyz_sorted[n][3] = the caller's float64 coordinates in that order (finite), order[n] = its order_out (sorted position -> point
+ *      index), keys_sorted[n] / grid = its sorted_keys_out / grid_out, cell_start = an optional p2w_cell_starts table of those keys
+ *      (NULL: runs are found by bisection).  The grid's cell must be at least the tolerance plus the fp32 rounding of the local
+ *      coordinates and of the key division (pointstowood_amd/cluster.py: safe_cell), so that every joined pair lies in adjacent cells.
+ * Out: labels_out[n] int64; counts_out[2] (device) = {number of kept clusters, number of points labelled -1}; pairs_out (optional,
+ *      device uint64) = the number of point pairs whose distance the link stage measured.
+ * `stages`: P2W_CLUSTER_ALL, or the stages one at a time in order (link, compress, number) on the same ws - the per-stage timing of
+ * tools/cluster_bench.py.  n < 2^31 - 1, tolerance finite and >= 0 (P2W_EINVAL otherwise).
+ * ws: 16-byte aligned, p2w_euclid_cluster_ws_bytes(n) bytes. */
+#define P2W_CLUSTER_LINK 1     /* union-find over the grid: every pair of adjacent cells measured once, the larger root hooked under the smaller */
+#define P2W_CLUSTER_COMPRESS 2 /* every point's root (= its component's smallest index) and the component sizes */
+#define P2W_CLUSTER_NUMBER 4   /* size filter, scan of the kept roots, labels and counts */
+#define P2W_CLUSTER_ALL 7
+size_t p2w_euclid_cluster_ws_bytes(int64_t n);
+int32_t p2w_euclid_cluster(const double* xyz_sorted, const int32_t* order, const uint64_t* keys_sorted, const int32_t* cell_start,
+                           const p2w_grid* grid, int64_t n, double tolerance, int64_t min_size, int64_t max_size, int32_t stages,
+                           int64_t* labels_out, int32_t* counts_out, uint64_t* pairs_out, void* ws, size_t ws_bytes,
+                           p2w_stream_t stream);
+
 /* PointCloudClassifier.compute_labels (predicter.py:112-127) over a neighbour table nbr[n,k] (indices into pred /
  * prob, deg[i] valid entries): pwood_out = median of the neighbours' probabilities (np.median: mean of the two middle
  * values for an even count); label_out: any_wood != 1 -> 1 if any neighbour's prediction > any_wood else 0;

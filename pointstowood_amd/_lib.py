@@ -29,6 +29,7 @@ PREC_OF = {"f16x3": PREC_F16X3, "fp16": PREC_F16, "bf16": PREC_BF16}
 GEMM_TILE_128, GEMM_TILE_256, GEMM_GENERIC_EPI, GEMM_ORDER_ROWS, GEMM_ORDER_COLS, GEMM_RESIDUAL_H = 1, 2, 4, 8, 16, 32   # P2W_GEMM_*
 GEMM_STREAMK, GEMM_NO_STREAMK = 64, 128
 SA_ITEM_256, SA_ITEM_128, SA_PACK8 = 1, 2, 4                                                       # P2W_SA_*
+CLUSTER_LINK, CLUSTER_COMPRESS, CLUSTER_NUMBER, CLUSTER_ALL = 1, 2, 4, 7                           # P2W_CLUSTER_*
 
 SIGNATURES = {
     "p2w_version": (_i32, []),
@@ -64,6 +65,8 @@ SIGNATURES = {
     "p2w_cell_starts_ws_bytes": (_sz, [C.c_int64]),
     "p2w_cell_starts": (_i32, [_vp, _i32, C.c_int64, _vp, _vp, _sz, _vp]),
     "p2w_vote": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _f32, _vp, _vp, _vp]),
+    "p2w_euclid_cluster_ws_bytes": (_sz, [C.c_int64]),
+    "p2w_euclid_cluster": (_i32, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_double, C.c_int64, C.c_int64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "p2w_tile_bbox": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "p2w_tile_bbox_count": (_i32, [_i32, _i32]),
     "p2w_stem": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp]),
