@@ -267,6 +267,45 @@ int32_t p2w_euclid_cluster(const double* xyz_sorted, const int32_t* order, const
                            int64_t* labels_out, int32_t* counts_out, uint64_t* pairs_out, void* ws, size_t ws_bytes,
                            p2w_stream_t stream);
 
+/* Exact fp64 kNN of one cloud against itself for k <= P2W_MAX_K_WIDE - the rows of the reference's path-length graph
+ * (pointstowood/utils/shortest_path.py:63-66: NearestNeighbors(n_neighbors=knn, leaf_size=15).fit(arr).kneighbors(arr), every point's
+ * own index in its row).  In: as p2w_euclid_cluster (the caller's float64 coordinates in the cell-sorted order of a p2w_voxel_sample
+ * call over fp32 coordinates local to the cloud's minimum, its order_out / sorted_keys_out / grid_out, an optional p2w_cell_starts
+ * table); `slack` >= how far the fp32 grid can misplace a point across a cell boundary (pointstowood_amd/pathlength.py: knn_slack).
+ * Any cell size gives the same result; it only sets how many cells a search visits.  Out: nbr_out[n, k] int32, row i = the k nearest
+ * points of point i ascending by (sqrt(((dx*dx + dy*dy) + dz*dz)) in float64, index).  1 <= k <= min(n, P2W_MAX_K_WIDE). */
+int32_t p2w_knn_wide_f64(const double* xyz_sorted, const int32_t* order, const uint64_t* keys_sorted, const int32_t* cell_start,
+                         const p2w_grid* grid, int64_t n, int32_t k, double slack, int32_t* nbr_out, p2w_stream_t stream);
+
+/* Graph growth of the path-length graph - array_to_graph (pointstowood/utils/shortest_path.py:80-187).  xyz[n][3] float64, nbr[n, k] =
+ * p2w_knn_wide_f64's rows (original indices), base = the root, kpairs / nbrs_threshold / nbrs_threshold_step / graph_threshold = the
+ * reference's arguments.  Frontier steps (:86-112) and gap steps (:115-176, the threshold raised in fp64 by one step per empty
+ * iteration) as the reference takes them; where no remaining row holds a processed point the growth stops (the reference raises its
+ * threshold for ever there) and the rest stays -1.  Out: step_out[n] = the step at which each point was processed (base 0, -1 never);
+ * edges_out[edge_cap][2] = the edges (g, e) in no particular order, duplicates and self-loops included; info_out (HOST, 6 int64) =
+ * {edges, step at which the loop stopped, gap steps, threshold raises, launches, 1 if points were left unreached}; threshold_out (HOST)
+ * = the final nbrs_threshold.  edge_cap >= n * 3 * (min(kpairs + 1, k)) always suffices (P2W_EWORKSPACE when the edges overflow).
+ * Blocks the host (the state is read back between launch batches and at every empty frontier).  nbrs_threshold_step finite and > 0.
+ * ws: 16-byte aligned, p2w_pathlen_grow_ws_bytes(n) bytes. */
+size_t p2w_pathlen_grow_ws_bytes(int64_t n);
+int32_t p2w_pathlen_grow(const double* xyz, const int32_t* nbr, int64_t n, int32_t k, int32_t base, int32_t kpairs, double nbrs_threshold,
+                         double nbrs_threshold_step, double graph_threshold, int32_t* step_out, int32_t* edges_out, int64_t edge_cap,
+                         int64_t* info_out, double* threshold_out, void* ws, size_t ws_bytes, p2w_stream_t stream);
+
+/* Shortest path lengths from `base` over an undirected edge list - extract_path_info (pointstowood/utils/shortest_path.py:195-238,
+ * networkx single_source_dijkstra).  edges[n_edges][2] int32 (duplicates and self-loops allowed), weights = the float64 distances of
+ * the endpoints' xyz.  Out: dist_out[n] = the minimum over paths of the left-fold fp64 sum (bit-equal to Dijkstra's), NaN where
+ * unreached; parent_out[n] (optional) = a neighbour u with dist[u] + w == dist[v], fewest hops first then smallest index (acyclic,
+ * every chain ends at base; -1 for base and unreached nodes); info_out (HOST, 3 int64) = {Bellman-Ford rounds, hop levels, launches}.
+ * Blocks the host.  ws: 16-byte aligned, p2w_pathlen_sssp_ws_bytes(n, n_edges) bytes. */
+size_t p2w_pathlen_sssp_ws_bytes(int64_t n, int64_t n_edges);
+int32_t p2w_pathlen_sssp(const double* xyz, const int32_t* edges, int64_t n_edges, int64_t n, int32_t base, double* dist_out,
+                         int32_t* parent_out, int64_t* info_out, void* ws, size_t ws_bytes, p2w_stream_t stream);
+
+/* w_out[e] = sqrt(((dx*dx + dy*dy) + dz*dz)) in float64 of the endpoints of edges[e] (int64 pairs): the weights of the graph object
+ * pointstowood_amd.pathlength.array_to_graph returns (shortest_path.py:241-266 add_nodes). */
+int32_t p2w_pathlen_weights(const double* xyz, const int64_t* edges, int64_t n_edges, double* w_out, p2w_stream_t stream);
+
 /* PointCloudClassifier.compute_labels (predicter.py:112-127) over a neighbour table nbr[n,k] (indices into pred /
  * prob, deg[i] valid entries): pwood_out = median of the neighbours' probabilities (np.median: mean of the two middle
  * values for an even count); label_out: any_wood != 1 -> 1 if any neighbour's prediction > any_wood else 0;

@@ -30,6 +30,7 @@ GEMM_TILE_128, GEMM_TILE_256, GEMM_GENERIC_EPI, GEMM_ORDER_ROWS, GEMM_ORDER_COLS
 GEMM_STREAMK, GEMM_NO_STREAMK = 64, 128
 SA_ITEM_256, SA_ITEM_128, SA_PACK8 = 1, 2, 4                                                       # P2W_SA_*
 CLUSTER_LINK, CLUSTER_COMPRESS, CLUSTER_NUMBER, CLUSTER_ALL = 1, 2, 4, 7                           # P2W_CLUSTER_*
+MAX_K_WIDE = 100                                                                                   # P2W_MAX_K_WIDE
 
 SIGNATURES = {
     "p2w_version": (_i32, []),
@@ -67,6 +68,13 @@ SIGNATURES = {
     "p2w_vote": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _f32, _vp, _vp, _vp]),
     "p2w_euclid_cluster_ws_bytes": (_sz, [C.c_int64]),
     "p2w_euclid_cluster": (_i32, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_double, C.c_int64, C.c_int64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "p2w_knn_wide_f64": (_i32, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _i32, C.c_double, _vp, _vp]),
+    "p2w_pathlen_grow_ws_bytes": (_sz, [C.c_int64]),
+    "p2w_pathlen_grow": (_i32, [_vp, _vp, C.c_int64, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, _vp, _vp, C.c_int64, _vp, _vp,
+                                _vp, _sz, _vp]),
+    "p2w_pathlen_sssp_ws_bytes": (_sz, [C.c_int64, C.c_int64]),
+    "p2w_pathlen_sssp": (_i32, [_vp, _vp, C.c_int64, C.c_int64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "p2w_pathlen_weights": (_i32, [_vp, _vp, C.c_int64, _vp, _vp]),
     "p2w_tile_bbox": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "p2w_tile_bbox_count": (_i32, [_i32, _i32]),
     "p2w_stem": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp]),
