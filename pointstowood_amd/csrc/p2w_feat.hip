@@ -646,13 +646,7 @@ extern "C" int32_t p2w_stem_h2_indexed(int32_t prec, const float* xyzr, int32_t 
 // wave-uniform (scalar loads, computed once per row instead of once per 4-column chunk); the lanes then sweep the row
 // 256 columns at a time with coalesced 16-byte loads of the coarse features.  The arithmetic per element is the same
 // as torch-scatter's: products and sums in neighbour order from 0, then a literal division.
-#ifndef P2W_IC_ROWS
-#define P2W_IC_ROWS 1   // swept 1..16 on the bench forward: 447 / 473 / 500 / 582 / 682 us for 1 / 2 / 4 / 8 / 16
-#endif
-constexpr int IC_ROWS = P2W_IC_ROWS;   // rows per wave (consecutive)
-#ifndef P2W_IC_PAIRS
-#define P2W_IC_PAIRS 1   // 0: one chunk per step (A/B: interpolation 0.355 -> 0.316 ms per bench step)
-#endif
+constexpr int IC_WAVE_ROWS = 1;   // rows per wave (consecutive); bench forward: 447 / 473 / 500 / 582 / 682 us for 1 / 2 / 4 / 8 / 16
 template <int PREC>
 __global__ __launch_bounds__(256) void interp_concat_kernel(const float* __restrict__ xc, int Fc, const float4* __restrict__ xyzr_c,
                                                             const float4* __restrict__ xyzr_f, const int* __restrict__ nbr,
@@ -660,8 +654,8 @@ __global__ __launch_bounds__(256) void interp_concat_kernel(const float* __restr
                                                             int Fs, int m, int q4, OutArgs o) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int q0 = (blockIdx.x * 4 + wave) * IC_ROWS;
-    for (int rr = 0; rr < IC_ROWS; ++rr) {
+    const int q0 = (blockIdx.x * 4 + wave) * IC_WAVE_ROWS;
+    for (int rr = 0; rr < IC_WAVE_ROWS; ++rr) {
         const int q = q0 + rr;   // wave-uniform
         if (q >= m) return;
         const int d = min(deg[q], kw);
@@ -679,10 +673,9 @@ __global__ __launch_bounds__(256) void interp_concat_kernel(const float* __restr
             if (s < 4) { js[s] = j; ws[s] = w; }
             den = den + w;
         }
-#if P2W_IC_PAIRS
         // the common shape (k <= 2 neighbours, interpolated columns only): two 256-column chunks per step with all their loads
         // issued before any arithmetic - the kernel waits for memory (VALU active 5 % of its wave cycles), so what counts is
-        // bytes in flight per lane
+        // bytes in flight per lane (A/B against one chunk per step: interpolation 0.355 -> 0.316 ms per bench step)
         int c_first = 4 * lane;
         if (d >= 1 && d <= 2 && Fs == 0) {
             for (; c_first + 256 < Fc && c_first + 256 < 4 * q4; c_first += 512) {
@@ -703,9 +696,6 @@ __global__ __launch_bounds__(256) void interp_concat_kernel(const float* __restr
             }
         }
         for (int c = c_first; c < 4 * q4; c += 256) {
-#else
-        for (int c = 4 * lane; c < 4 * q4; c += 256) {
-#endif
             float v[4] = {0.f, 0.f, 0.f, 0.f};
             if (c < Fc) {
                 float4 num = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -750,7 +740,7 @@ static int32_t interp_launch(int32_t prec, const float* xc, int32_t Fc, const fl
     const int hcols = out_h2 ? (ldh < hfull ? ldh : hfull) : 0;   // ldh is the pitch: the row may continue with columns another producer owns
     const int width = (out ? ldo : 0) > hcols ? ldo : hcols;
     OutArgs o = {out, out ? ldo : 0, static_cast<_Float16*>(out_h2), out_h2 ? ldh : 0, hcols, nullptr, nullptr, 0};
-    P2W_LAUNCH_PREC(prec, interp_concat_kernel, p2w_cdiv(m, 4 * IC_ROWS), 256, p2w_s(stream),
+    P2W_LAUNCH_PREC(prec, interp_concat_kernel, p2w_cdiv(m, 4 * IC_WAVE_ROWS), 256, p2w_s(stream),
         xc, Fc, reinterpret_cast<const float4*>(xyzr_c), reinterpret_cast<const float4*>(xyzr_f), nbr, deg, kw, skip, Fs, m,
         width >> 2, o);
     return P2W_LAUNCH_STATUS();

@@ -11,9 +11,9 @@
 // pad columns are zero.  Weights are packed the same way, one row per output channel: [N_pad][planes * K_pad] of W * 2^e.
 // Either way the 64 halfs a GEMM slab consumes of a row are ONE 128-byte cache line.
 //
-// MFMAs: the production GEMM (gemm_hp_kernel) uses v_mfma_f32_16x16x32_{f16,bf16} (layout at h_mfma16 below); the fused
-// PointNetConv and the diagnostic one-workgroup-per-tile GEMM use v_mfma_f32_32x32x16_{f16,bf16}: lane l supplies
-// A[row l&31][k = 8*(l>>5) + 0..7] (16 contiguous bytes), B alike; C/D: col = l&31, row = (reg&3) + 8*(reg>>2) + 4*(l>>5).
+// MFMAs: the GEMM (gemm_hp_kernel) uses v_mfma_f32_16x16x32_{f16,bf16} (layout at h_mfma16 below); the fused PointNetConv
+// uses v_mfma_f32_32x32x16_{f16,bf16}: lane l supplies A[row l&31][k = 8*(l>>5) + 0..7] (16 contiguous bytes), B alike;
+// C/D: col = l&31, row = (reg&3) + 8*(reg>>2) + 4*(l>>5).
 // f16x3 contracts a_lo*w_hi + a_hi*w_lo + a_hi*w_hi (three MFMAs per product, fp32 accumulate); the single-plane modes issue one.
 #pragma once
 #include "p2w_common.h"
@@ -30,25 +30,7 @@ typedef __attribute__((address_space(3))) void* lds_vp;
 typedef const __attribute__((address_space(1))) void* glb_vp;
 
 constexpr int H_BK = 32;   // k per plane of a PointNetConv slab
-#ifndef P2W_SA_PREFETCH_FRAGS
-#define P2W_SA_PREFETCH_FRAGS 1   // 0: the previous form (A/B: fused PointNetConv class -2.9 %)
-#ifndef P2W_SA_PK_FMA
-#define P2W_SA_PK_FMA 0           // 1: the producer's layer-1 correction on packed fp32 FMAs (v_pk_fma_f32: same bits) - measured +3 % on the
-                                  // class (1.88 against 1.82 ms, alternating processes): the packed form issues no faster and co-executes worse with the MFMAs
-#endif
-#endif
 constexpr int SA_EPI_COLS = 1024;   // capacity of the fused PointNetConv's LDS table of per-column epilogue parameters (C2 limit)
-
-
-#if defined(P2W_GEMM_STAMP) || defined(P2W_SA_STAMP)   // diagnostic builds (tools/gemm_stamps.py, tools/sa_stamps.py): in-kernel cycle stamps
-__device__ __forceinline__ unsigned long long p2w_stamp() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#endif
 
 template <int PREC> struct HCfg {
     static constexpr int planes = PREC == 0 ? 2 : 1;      // 16-bit planes per H row
@@ -64,7 +46,7 @@ __device__ __forceinline__ f32x16 h_mfma(h8 a, h8 b, f32x16 c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
 
-// The production GEMM uses the 16x16x32 shape: lane l supplies A[row l&15][k = 8*(l>>4) + 0..7] (one 16-byte chunk: a whole
+// The GEMM uses the 16x16x32 shape: lane l supplies A[row l&15][k = 8*(l>>4) + 0..7] (one 16-byte chunk: a whole
 // 32-k plane row per instruction), B alike; C/D: col = l&15, row = 4*(l>>4) + reg.  Same FLOPs per cycle as 32x32x16, but
 // MI355X holds a higher clock on it (MI355X_MICROARCH.md, DVFS item 7): GEMM class -15 % in a same-box A/B.
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -172,9 +154,7 @@ static inline int p2w_cu_count() {
 // ------------------------------------------------------------------------------------------------
 // epilogues
 // ------------------------------------------------------------------------------------------------
-#ifndef P2W_INTERP_DEPTH
-#define P2W_INTERP_DEPTH 2   // steps of source rows in flight in the interpolated-residual epilogue
-#endif
+constexpr int RI_DEPTH = 2;   // steps of source rows in flight in the interpolated-residual epilogue
 struct EpiArgs {
     const float *bias, *sc0, *sh0, *sc1, *sh1, *residual;
     int ldr, relu0, relu1, relu2, relu_final;
@@ -236,13 +216,13 @@ __device__ __forceinline__ float row16_sum(float v) {
     return v;
 }
 
-// Column ownership.  The W rows of a stage are staged PERMUTED (w_stage_row below): LDS row 32 t + r of a wave's column
-// range holds output channel 64 (t >> 1) + 2 r + (t & 1), so lane r of accumulator tiles 2 jp and 2 jp + 1 holds the two
-// ADJACENT columns c = col0 + 64 jp + 2 r and c + 1 of the same rows: an H word (two fp16) or a float2 per lane and row
-// without any cross-lane exchange, per-column parameters as float2 loads.
-__device__ __forceinline__ int w_stage_row(int rho) {   // LDS W row (within the workgroup's BN rows) -> W row (output channel)
-    const int t = rho >> 5, r = rho & 31;
-    return 64 * (t >> 1) + 2 * r + (t & 1);
+// Column ownership.  The W rows of a stage are staged PERMUTED (w_stage_row16): LDS row 16 t + c of a wave's column range
+// holds output channel 32 (t >> 1) + 2 c + (t & 1), so lane c of the 16 x 16 accumulator tiles 2 jq and 2 jq + 1 holds the two
+// ADJACENT columns col0 + 32 jq + 2 c and + 1 of rows 16 it + 4 (lane >> 4) + reg: an H word (two fp16) or a float2 per lane
+// and row without any cross-lane exchange, per-column parameters as float2 loads.
+__device__ __forceinline__ int w_stage_row16(int rho) {
+    const int t = rho >> 4, c = rho & 15;
+    return 32 * (t >> 1) + 2 * c + (t & 1);
 }
 
 // EF >= 0: compile-time flags (1 relu0, 2 sc0, 4 relu1, 8 sc1, 16 relu2, 32 residual, 64 relu_final, 128 fp32 out, 256 H out)
@@ -250,151 +230,6 @@ __device__ __forceinline__ int w_stage_row(int rho) {   // LDS W row (within the
 // float2 parameter / residual / fp32 accesses, the residual of the next row in flight while a row is finished and stored
 // (on gfx950 loads and stores retire through one counter: a load waited for right behind its issue drains every store).
 // EF < 0: runtime flags, every access guarded (edge tiles, odd sizes); pad columns [N, ldh) of the H rows are written as zeros.
-template <int PREC, int RT, int CT, int EF>
-__device__ __forceinline__ void gemm_epilogue_il(const f32x16 (&acc)[RT][CT], const EpiArgs& ep, float wscale, int row0, int col0,
-                                                 int lane, int M, int N, const OutArgs& o) {
-    static_assert(CT % 2 == 0, "column tiles come in interleaved pairs");
-    constexpr bool GEN = EF < 0;
-    constexpr int JP = CT / 2, NSTEP = RT * 16;
-    const bool R0 = GEN ? ep.relu0 != 0 : (EF & 1) != 0, S0 = GEN ? ep.sc0 != nullptr : (EF & 2) != 0;
-    const bool R1 = GEN ? ep.relu1 != 0 : (EF & 4) != 0, S1 = GEN ? ep.sc1 != nullptr : (EF & 8) != 0;
-    const bool R2 = GEN ? ep.relu2 != 0 : (EF & 16) != 0, RES = GEN ? ep.residual != nullptr : (EF & 32) != 0;
-    const bool RF = GEN ? ep.relu_final != 0 : (EF & 64) != 0, OF = GEN ? o.f32 != nullptr : (EF & 128) != 0;
-    const bool OH = GEN ? o.h2 != nullptr : (EF & 256) != 0;
-    const int r = lane & 31, h = lane >> 5;
-    const int cb = col0 + 2 * r;   // even column of pair 0; pair jp: + 64 jp
-    fpair bias[JP], s0[JP], t0[JP], s1[JP], t1[JP];
-#pragma unroll
-    for (int jp = 0; jp < JP; ++jp) {
-        const int c = cb + 64 * jp;
-        bias[jp] = fpair{0.f, 0.f}; s0[jp] = fpair{1.f, 1.f}; t0[jp] = fpair{0.f, 0.f}; s1[jp] = fpair{1.f, 1.f}; t1[jp] = fpair{0.f, 0.f};
-        if constexpr (GEN) {
-#pragma unroll
-            for (int e = 0; e < 2; ++e)
-                if (c + e < N) {
-                    if (ep.bias) bias[jp][e] = ep.bias[c + e];
-                    if (S0) { s0[jp][e] = ep.sc0[c + e]; t0[jp][e] = ep.sh0[c + e]; }
-                    if (S1) { s1[jp][e] = ep.sc1[c + e]; t1[jp][e] = ep.sh1[c + e]; }
-                }
-        } else {
-            if (ep.bias) bias[jp] = *reinterpret_cast<const fpair*>(ep.bias + c);
-            if (S0) { s0[jp] = *reinterpret_cast<const fpair*>(ep.sc0 + c); t0[jp] = *reinterpret_cast<const fpair*>(ep.sh0 + c); }
-            if (S1) { s1[jp] = *reinterpret_cast<const fpair*>(ep.sc1 + c); t1[jp] = *reinterpret_cast<const fpair*>(ep.sh1 + c); }
-        }
-    }
-    auto row_of = [&](int st) { const int i = st >> 4, reg = st & 15; return row0 + 32 * i + (reg & 3) + 8 * (reg >> 2) + 4 * h; };
-    auto value = [&](float a, float b, float s0v, float t0v, float s1v, float t1v, float res) {
-        float v = fmaf(a, wscale, b);
-        if (R0) v = fmaxf(v, 0.f);
-        if (S0) v = fmaf(v, s0v, t0v);
-        if (R1) v = fmaxf(v, 0.f);
-        if (S1) v = fmaf(v, s1v, t1v);
-        if (R2) v = fmaxf(v, 0.f);
-        if (RES) v += res;
-        if (RF) v = fmaxf(v, 0.f);
-        return v;
-    };
-    fpair rcur[JP], rnxt[JP];
-    auto load_res = [&](fpair (&dst)[JP], int st) {   // specialised path only
-        const float* rp = ep.residual + ((unsigned)row_of(st) * (unsigned)ep.ldr + (unsigned)cb);
-#pragma unroll
-        for (int jp = 0; jp < JP; ++jp) dst[jp] = *reinterpret_cast<const fpair*>(rp + 64 * jp);
-    };
-#pragma unroll
-    for (int jp = 0; jp < JP; ++jp) { rcur[jp] = fpair{0.f, 0.f}; rnxt[jp] = fpair{0.f, 0.f}; }
-    if constexpr (!GEN) {
-        if (RES) load_res(rcur, 0);
-    }
-#pragma unroll
-    for (int st = 0; st < NSTEP; ++st) {
-        const int i = st >> 4, reg = st & 15;
-        const int row = row_of(st);
-        if constexpr (!GEN) {
-            if (RES && st + 1 < NSTEP) load_res(rnxt, st + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            float* fp = OF ? o.f32 + ((unsigned)row * (unsigned)o.ldo + (unsigned)cb) : nullptr;
-            _Float16* hp = nullptr;
-            if (OH) {
-                if constexpr (PREC == 0) hp = o.h2 + ((unsigned)row * (unsigned)(2 * o.ldh) + (unsigned)(64 * (cb >> 5) + (cb & 31)));
-                else hp = o.h2 + ((unsigned)row * (unsigned)o.ldh + (unsigned)cb);
-            }
-#pragma unroll
-            for (int jp = 0; jp < JP; ++jp) {
-                const float va = value(acc[i][2 * jp][reg], bias[jp][0], s0[jp][0], t0[jp][0], s1[jp][0], t1[jp][0], rcur[jp][0]);
-                const float vb = value(acc[i][2 * jp + 1][reg], bias[jp][1], s0[jp][1], t0[jp][1], s1[jp][1], t1[jp][1], rcur[jp][1]);
-                if (OF) *reinterpret_cast<fpair*>(fp + 64 * jp) = fpair{va, vb};
-                if (OH) {
-                    if constexpr (PREC == 0) {
-                        unsigned hw, lw;
-                        split_pair(va, vb, hw, lw);
-                        *reinterpret_cast<unsigned*>(hp + 128 * jp) = hw;        // 64 columns further = two [hi32 | lo32] blocks
-                        *reinterpret_cast<unsigned*>(hp + 128 * jp + 32) = lw;
-                    } else {
-                        *reinterpret_cast<unsigned*>(hp + 64 * jp) = pack_pair<PREC>(va, vb);
-                    }
-                }
-            }
-            if (RES) {
-#pragma unroll
-                for (int jp = 0; jp < JP; ++jp) rcur[jp] = rnxt[jp];
-            }
-        } else {
-            if (row < M) {
-#pragma unroll
-                for (int jp = 0; jp < JP; ++jp) {
-                    const int c = cb + 64 * jp;
-                    float v[2];
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        const bool cv = c + e < N;
-                        const float res = (RES && cv) ? ep.residual[(size_t)row * ep.ldr + c + e] : 0.f;
-                        v[e] = value(acc[i][2 * jp + e][reg], bias[jp][e], s0[jp][e], t0[jp][e], s1[jp][e], t1[jp][e], res);
-                        if (!cv) v[e] = 0.f;                       // pad columns of an H row must be zero
-                        if (OF && cv) o.f32[(size_t)row * o.ldo + c + e] = v[e];
-                    }
-                    if (OH && c < o.hcols) h_store2<PREC>(o.h2, o.ldh, row, c, v[0], v[1]);
-                }
-            }
-        }
-    }
-}
-
-// s_waitcnt immediate of gfx9: vmcnt[3:0] | expcnt << 4 | lgkmcnt << 8 | vmcnt[5:4] << 14 (expcnt / lgkmcnt left at their maxima)
-constexpr int p2w_vmcnt_imm(int n) { return (n & 15) | (7 << 4) | (15 << 8) | ((n >> 4) << 14); }
-
-// WAIT_OLDER (persistent kernel): behind the epilogue, wait until everything this wave issued BEFORE the epilogue has
-// retired (the next tile's first-slab DMA) without waiting for the epilogue's own stores: loads, stores and LDS-DMA retire
-// in order through one counter, so "at most n outstanding" with n = the number of stores the epilogue just issued (capped at
-// the counter's 63) is exactly that.  The wait sits here, in the branch that knows n at compile time, through the builtin:
-// the compiler's scoreboard then knows on every path that no load is pending (the guarded path drains completely).
-template <int PREC, int RT, int CT, bool WAIT_OLDER = false>
-__device__ __forceinline__ void gemm_epilogue_dispatch(const f32x16 (&acc)[RT][CT], const EpiArgs& ep, float wscale, int row0,
-                                                       int col0, int lane, int M, int N, const OutArgs& o, int ef) {
-    const bool full = (row0 + 32 * RT <= M) && (col0 + 32 * CT <= N) && ef != 0;
-    if (full) {
-        switch (ef) {
-#define P2W_EPI_CASE(E) case E: { \
-            gemm_epilogue_il<PREC, RT, CT, E>(acc, ep, wscale, row0, col0, lane, M, N, o); \
-            constexpr int n_st = RT * 16 * (CT / 2) * (((E) & 128 ? 1 : 0) + ((E) & 256 ? (PREC == 0 ? 2 : 1) : 0)); \
-            if constexpr (WAIT_OLDER) __builtin_amdgcn_s_waitcnt(p2w_vmcnt_imm(n_st < 63 ? n_st : 63)); \
-            return; }
-            P2W_EPI_CASE(128) P2W_EPI_CASE(257) P2W_EPI_CASE(263) P2W_EPI_CASE(287) P2W_EPI_CASE(480) P2W_EPI_CASE(224)
-            P2W_EPI_CASE(131) P2W_EPI_CASE(259) P2W_EPI_CASE(387) P2W_EPI_CASE(129)
-#undef P2W_EPI_CASE
-            default: break;
-        }
-    }
-    gemm_epilogue_il<PREC, RT, CT, -1>(acc, ep, wscale, row0, col0, lane, M, N, o);
-    if constexpr (WAIT_OLDER) __builtin_amdgcn_s_waitcnt(p2w_vmcnt_imm(0));
-}
-
-// ---- the same epilogue for 16 x 16 accumulator tiles (gemm_hp_kernel) ----
-// W rows are staged by w_stage_row16: LDS row 16 t + c of a wave's column range holds output channel 32 (t >> 1) + 2 c + (t & 1),
-// so lane c of tiles 2 jq, 2 jq + 1 holds the adjacent columns col0 + 32 jq + 2 c (+1) of rows 16 it + 4 (lane >> 4) + reg.
-__device__ __forceinline__ int w_stage_row16(int rho) {
-    const int t = rho >> 4, c = rho & 15;
-    return 32 * (t >> 1) + 2 * c + (t & 1);
-}
 template <int PREC, int RT16, int CT16, int EF, bool DOTK = false>   // DOTK: the row-dot kernel (the plain kernel compiles none of it)
 __device__ __forceinline__ void gemm_epilogue_16(const f32x4 (&acc)[RT16][CT16], const EpiArgs& ep, float wscale, int row0, int col0,
                                                  int lane, int M, int N, const OutArgs& o, bool seen_report = true) {
@@ -452,7 +287,7 @@ __device__ __forceinline__ void gemm_epilogue_16(const f32x4 (&acc)[RT16][CT16],
     // interpolated residual: a ring of RI_D steps' raw source rows (two dependent gathers - record, then the rows it names -
     // each issued ahead of its use: the record of step st + RI_D + 1 and the rows of step st + RI_D during step st; what bounds
     // these launches is gather bytes in flight per CU, not arithmetic)
-    constexpr int RI_D = RI_OK ? (P2W_INTERP_DEPTH < NSTEP ? P2W_INTERP_DEPTH : NSTEP) : 1;
+    constexpr int RI_D = RI_OK ? (RI_DEPTH < NSTEP ? RI_DEPTH : NSTEP) : 1;
     fpair z0r[RI_D][RI_OK ? JQ : 1], z1r[RI_D][RI_OK ? JQ : 1];
     float a0r[RI_D], a1r[RI_D];
     int4 m_nxt = make_int4(0, 0, 0, 0);
@@ -525,9 +360,7 @@ __device__ __forceinline__ void gemm_epilogue_16(const f32x4 (&acc)[RT16][CT16],
             for (int jq = 0; jq < JQ; ++jq) {
                 const float va = value(acc[it][2 * jq][reg], bias[jq][0], s0[jq][0], t0[jq][0], s1[jq][0], t1[jq][0], rcur[jq][0]);
                 const float vb = value(acc[it][2 * jq + 1][reg], bias[jq][1], s0[jq][1], t0[jq][1], s1[jq][1], t1[jq][1], rcur[jq][1]);
-#if !defined(P2W_RANGE_AB) || P2W_RANGE_AB < 3   // (diagnostic builds, tools/range_watch_ab.py: 1 no compares, 2 no stores, 3 no tracking)
                 m4 = fmaxf(m4, fmaxf(fabsf(va), fabsf(vb)));     // (one v_max3 per column pair)
-#endif
                 if (DOT) dsum = fmaf(vb, dw[jq][1], fmaf(va, dw[jq][0], dsum));
                 if (OF) *reinterpret_cast<fpair*>(fp + 32 * jq) = fpair{va, vb};
                 if (OH) {
@@ -541,15 +374,11 @@ __device__ __forceinline__ void gemm_epilogue_16(const f32x4 (&acc)[RT16][CT16],
                     }
                 }
             }
-#if !defined(P2W_RANGE_AB) || P2W_RANGE_AB == 2
             if (reg == 3) {   // the maximum of four row steps goes into the scalar masks: two compares per 4 x JQ column pairs
                 r_over |= __ballot(!(m4 <= P2W_RANGE_HI));
                 r_seen |= __ballot(m4 > P2W_RANGE_LO);
                 m4 = 0.f;
             }
-#elif P2W_RANGE_AB == 1
-            if (reg == 3) { asm volatile("" :: "v"(m4)); m4 = 0.f; }
-#endif
             if (DOT) {   // the four rows of a lane (reg 0..3) are consecutive: one 16-byte store per row tile by the lanes of column 0
                 dot4[reg] = row16_sum(dsum);
                 if (reg == 3 && c16 == 0)
@@ -596,14 +425,20 @@ __device__ __forceinline__ void gemm_epilogue_16(const f32x4 (&acc)[RT16][CT16],
             }
         }
     }
-#if !defined(P2W_RANGE_AB) || P2W_RANGE_AB == 1
     // (wave-uniform branch.  OVER is reported by every tile; SEEN - "the tensor has values of ordinary size", true of nearly every
     // wave - only where the caller asks for it: a persistent workgroup's FIRST tile.  The report stores were the watch's whole
-    // cost: 8 000 of them per launch +0.1 ms on the class, the tracking and the compares nothing - tools/range_watch_ab.py)
+    // cost: 8 000 of them per launch +0.1 ms on the class, the tracking and the compares nothing)
     if (ep.range) range_commit(ep.range, r_over != 0ull, seen_report && r_seen != 0ull, lane);
-#endif
 }
 
+// s_waitcnt immediate of gfx9: vmcnt[3:0] | expcnt << 4 | lgkmcnt << 8 | vmcnt[5:4] << 14 (expcnt / lgkmcnt left at their maxima)
+constexpr int p2w_vmcnt_imm(int n) { return (n & 15) | (7 << 4) | (15 << 8) | ((n >> 4) << 14); }
+
+// WAIT_OLDER (persistent kernel): behind the epilogue, wait until everything this wave issued BEFORE the epilogue has
+// retired (the next tile's first-slab DMA) without waiting for the epilogue's own stores: loads, stores and LDS-DMA retire
+// in order through one counter, so "at most n outstanding" with n = the number of stores the epilogue just issued (capped at
+// the counter's 63) is exactly that.  The wait sits here, in the branch that knows n at compile time, through the builtin:
+// the compiler's scoreboard then knows on every path that no load is pending (the guarded path drains completely).
 template <int PREC, int RT16, int CT16, bool WAIT_OLDER = false, bool DOTK = false>
 __device__ __forceinline__ void gemm_epilogue_dispatch16(const f32x4 (&acc)[RT16][CT16], const EpiArgs& ep, float wscale, int row0,
                                                          int col0, int lane, int M, int N, const OutArgs& o, int ef,
@@ -651,210 +486,23 @@ __device__ __forceinline__ void gemm_epilogue_dispatch16(const f32x4 (&acc)[RT16
 // (global_load_lds_dwordx4: no VGPR round trip, no ds_write) into a 2-stage ring; one barrier per slab, the next
 // slab's DMA is in flight during the whole MFMA phase of the current one.
 // A slab takes 64 halfs = ONE 128-byte cache line of every A / W row (f16x3: [hi(32 k) | lo(32 k)]; single-plane: 64 k),
-// stored as a 128-byte LDS row of 8 chunks with an XOR swizzle (details at the DMA setup below): conflict-free
-// ds_read_b128 fragments, and the image, the DMA pattern and the fragment reads are the same in every precision - only
-// the MFMA pairing differs.  W rows are staged permuted (w_stage_row) so that a lane owns adjacent output columns.
+// stored as a 128-byte LDS row of 8 chunks with an XOR swizzle: conflict-free ds_read_b128 fragments, and the image, the
+// DMA pattern and the fragment reads are the same in every precision - only the MFMA pairing differs.  W rows are staged
+// permuted (w_stage_row16) so that a lane owns adjacent output columns.
 // Out-of-range A rows are clamped to M-1 (their results are never stored); K padding is zero in both operands.
-// ------------------------------------------------------------------------------------------------
-template <int PREC, int WR, int WC, int RT, int CT>   // waves WR x WC, wave tile (32*RT) x (32*CT)
-__global__ __launch_bounds__(64 * WR * WC, 2) void gemm_h2g_kernel(const _Float16* __restrict__ A, int ldh_a,
-                                                                const _Float16* __restrict__ Wh, size_t plane, float wscale,
-                                                                int M, int N, int Kpad, int nMt, int nNt, EpiArgs ep,
-                                                                OutArgs o, int dbg_, int ef, int tmode) {
-    // dbg (profiling ablations): 1 = skip the epilogue, 2 = issue only the first slab's DMA, 4 = skip the MFMAs,
-    // 8 = fragments loaded once, 16 = no barrier, 32 = every workgroup reads row tile 0.  Compiled in only by diagnostic
-    // builds (P2W_EXTRA_CFLAGS=-DP2W_GEMM_ABLATE): this kernel sits at 256 VGPRs and every extra path costs scratch.
-#ifdef P2W_GEMM_ABLATE
-    const int dbg = dbg_;
-#else
-    constexpr int dbg = 0;
-    (void)dbg_;
-#endif
-    constexpr int KS = HCfg<PREC>::kslab;
-    constexpr int BM = 32 * RT * WR, BN = 32 * CT * WC, NW = WR * WC;
-    constexpr int A_CH = 8 * BM, STAGE_CH = A_CH + 8 * BN;   // 16-byte chunks per stage (2 planes x rows x 4)
-#ifndef P2W_GEMM_DMA_MODE
-#define P2W_GEMM_DMA_MODE 2
-#endif
-    // DMA issue (A/B switch P2W_GEMM_DMA_MODE): 0 = every wave issues its share as one burst behind the barrier;
-    // 1 = every wave spreads its share over the first half of its MFMAs; 2 (8-wave tiles) = waves 0..3 issue the whole
-    // stage behind the barrier while waves 4..7 - their SIMD partners, which the hardware's oldest-first arbitration makes
-    // the losers of every slab (in-kernel stamps: wave 0 waits 39 % of the loop at the barrier, wave 4 4 %) - start on the
-    // MFMAs at once: the issue time of one half is the other half's uncontested MFMA time.
-    constexpr int DMA_MODE = (P2W_GEMM_DMA_MODE == 2 && NW != 8) ? 1 : P2W_GEMM_DMA_MODE;
-    constexpr int NWI = DMA_MODE == 2 ? NW / 2 : NW;          // issuing waves
-    constexpr int NI = STAGE_CH / 64 / NWI;                  // DMA instructions per issuing wave per stage
-    static_assert(STAGE_CH % (64 * NWI) == 0, "stage must split evenly over the issuing waves");
-    __shared__ __attribute__((aligned(16))) char S[2 * STAGE_CH * 16];
-    int mt, nt;
-    if (!tile_coords(nMt, nNt, &mt, &nt, tmode)) return;
-    const int m0 = mt * BM, n0 = nt * BN;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), wr = wave / WC, wc = wave % WC;
-    // Global layout of one slab row: 64 halfs = 128 contiguous bytes (a whole cache line) - single-plane: k0..k0+63;
-    // f16x3 (interleaved H layout): [hi(k0..k0+31) | lo(k0..k0+31)].  So a slab advances 64 halfs in every precision.
-    const size_t a_pitch = (size_t)HCfg<PREC>::planes * ldh_a, w_pitch = (size_t)HCfg<PREC>::planes * Kpad;   // halfs per row
-    (void)plane;
-
-    // LDS image of a stage: rows of 128 B = 8 chunks of 16 B, A rows 0..BM-1 then B rows.  Chunk c of a row (c>>2 = plane:
-    // hi / lo, or the k half of a single-plane slab; c&3 = 8 k each) is stored at chunk position c ^ ((row >> 1) & 7), so a
-    // ds_read_b128 of one chunk index by 16 different rows spreads over all 16 slots of the 256-byte bank row: conflict-free.
-    // A DMA piece (one wave-instruction, 1 KiB) = 8 image rows: lane L -> row 8g + (L >> 3), stored chunk L & 7, reading the
-    // source chunk (L & 7) ^ swizzle: 8 rows x 128 contiguous bytes = 8 whole cache lines per piece.
-    const _Float16* src[NI];
-    int dstc[NI];
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        const int g = (wave % NWI) + NWI * i;
-        const int row = 8 * g + (lane >> 3);
-        const int c = (lane & 7) ^ ((row >> 1) & 7);
-        if (g < BM / 8) {
-            const int grow = (dbg & 32) ? row : min(m0 + row, M - 1);   // dbg 32: every workgroup reads row tile 0 (no A traffic)
-            src[i] = A + (size_t)grow * a_pitch + 8 * c;
-        } else {
-            src[i] = Wh + (size_t)(n0 + w_stage_row(row - BM)) * w_pitch + 8 * c;
-        }
-        dstc[i] = g * 64;
-    }
-    auto issue_piece = [&](int i, int stage, int k0) {
-        __builtin_amdgcn_global_load_lds((glb_vp)(src[i] + k0), (lds_vp)(S + ((size_t)stage * STAGE_CH + dstc[i]) * 16), 16, 0, 0);
-    };
-    const bool issuer = wave < NWI;   // wave-uniform
-    auto issue = [&](int stage, int k0) {
-        if (issuer) {
-#pragma unroll
-            for (int i = 0; i < NI; ++i) issue_piece(i, stage, k0);
-        }
-    };
-
-    // fragment read offsets (bytes within a stage) of plane 0, k step 0; plane 1 = ^ 64 (chunk bit 2), k step 1 = ^ 32 (bit 1)
-    const int r = lane & 31, h = lane >> 5;
-    int offA[RT], offB[CT];
-#pragma unroll
-    for (int t = 0; t < RT; ++t) {
-        const int ra = wr * 32 * RT + 32 * t + r;
-        offA[t] = (ra * 8 + (h ^ ((ra >> 1) & 7))) * 16;
-    }
-#pragma unroll
-    for (int t = 0; t < CT; ++t) {
-        const int rb = BM + wc * 32 * CT + 32 * t + r;
-        offB[t] = (rb * 8 + (h ^ ((rb >> 1) & 7))) * 16;
-    }
-
-    f32x16 acc[RT][CT];
-#pragma unroll
-    for (int i = 0; i < RT; ++i)
-#pragma unroll
-        for (int j = 0; j < CT; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    const int nslab = Kpad / KS;
-#ifdef P2W_GEMM_STAMP
-    unsigned long long t_wait = 0, t_rd = 0;
-    const unsigned long long t_start = p2w_stamp();
-#endif
-    issue(0, 0);
-    h8 ah[RT], al[RT], bh[CT], bl[CT];   // plane 0 / plane 1 fragments
-    if (dbg & 8) {   // diagnostic: fragments loaded once, the loop below is MFMA (+ optional barrier) only
-        const char* st0 = S;
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < RT; ++t) { ah[t] = *reinterpret_cast<const h8*>(st0 + offA[t]); al[t] = *reinterpret_cast<const h8*>(st0 + (offA[t] ^ 64)); }
-#pragma unroll
-        for (int t = 0; t < CT; ++t) { bh[t] = *reinterpret_cast<const h8*>(st0 + offB[t]); bl[t] = *reinterpret_cast<const h8*>(st0 + (offB[t] ^ 64)); }
-    }
-    // One slab: barrier, the next slab's DMA, fragment reads + MFMAs of this slab.  The NI DMA pieces a wave issues are
-    // spread over the first half of the slab's MFMAs (sched_group_barrier) instead of going out as one burst behind the
-    // barrier: a piece costs ~60-180 issue cycles, and with every wave of the workgroup re-aligned by the barrier a burst
-    // leaves all four MFMA pipes idle for ~1000 cycles of a ~3000-cycle slab.
-    auto slab = [&](int s, auto more_c) {
-        constexpr bool MORE = decltype(more_c)::value;
-#ifdef P2W_GEMM_STAMP
-        const unsigned long long t_a = p2w_stamp();
-#endif
-        if (!(dbg & 16)) __syncthreads();  // = s_waitcnt vmcnt(0) + barrier: slab s has landed for every wave, slab s-1's buffer is free
-#ifdef P2W_GEMM_STAMP
-        const unsigned long long t_b = p2w_stamp();
-        t_wait += t_b - t_a;
-#endif
-        if (DMA_MODE != 1 && MORE && !(dbg & 2)) issue((s + 1) & 1, (s + 1) * 64);
-        const char* st = S + (size_t)(s & 1) * STAGE_CH * 16;
-        if (dbg & 4) return;
-        constexpr int NG = 2 * RT * CT;                                  // MFMA groups (one per tile pair and k step) of a slab
-        constexpr int GAP = (NG / (2 * NI)) > 0 ? NG / (2 * NI) : 1;     // groups between two pieces: all out in the first half
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            if (!(dbg & 8)) {
-#pragma unroll
-            for (int t = 0; t < RT; ++t) {
-                ah[t] = *reinterpret_cast<const h8*>(st + (offA[t] ^ (kk << 5)));
-                al[t] = *reinterpret_cast<const h8*>(st + (offA[t] ^ (kk << 5) ^ 64));
-            }
-#pragma unroll
-            for (int t = 0; t < CT; ++t) {
-                bh[t] = *reinterpret_cast<const h8*>(st + (offB[t] ^ (kk << 5)));
-                bl[t] = *reinterpret_cast<const h8*>(st + (offB[t] ^ (kk << 5) ^ 64));
-            }
-            }
-#if defined(P2W_GEMM_STAMP) && P2W_GEMM_STAMP > 1
-            {   // level 2: time until this half slab's fragments are in registers (drains the reads: perturbs the schedule)
-                const unsigned long long t_c = p2w_stamp();
-                asm volatile("" :: "v"(ah[0]), "v"(al[0]), "v"(bh[0]), "v"(bl[0]));
-                const unsigned long long t_d = p2w_stamp();
-                t_rd += t_d - t_c;
-            }
-#endif
-#pragma unroll
-            for (int i = 0; i < RT; ++i)
-#pragma unroll
-                for (int j = 0; j < CT; ++j) {
-                    if constexpr (PREC == 0) {
-                        acc[i][j] = h_mfma<PREC>(al[i], bh[j], acc[i][j]);
-                        acc[i][j] = h_mfma<PREC>(ah[i], bl[j], acc[i][j]);
-                        acc[i][j] = h_mfma<PREC>(ah[i], bh[j], acc[i][j]);
-                    } else {   // planes are the two k halves of the slab
-                        acc[i][j] = h_mfma<PREC>(ah[i], bh[j], acc[i][j]);
-                        acc[i][j] = h_mfma<PREC>(al[i], bl[j], acc[i][j]);
-                    }
-                    if constexpr (DMA_MODE == 1) {
-                        const int g = (kk * RT + i) * CT + j;             // compile-time after unrolling
-                        if (MORE && !(dbg & 2) && (g % GAP) == GAP - 1 && g / GAP < NI) {
-                            issue_piece(g / GAP, (s + 1) & 1, (s + 1) * 64);
-                            __builtin_amdgcn_sched_barrier(0);            // keep the piece between its two MFMA groups
-                        }
-                    }
-                }
-        }
-    };
-    for (int s = 0; s + 1 < nslab; ++s) slab(s, std::true_type{});
-    slab(nslab - 1, std::false_type{});
-    if (dbg & 1) {
-        if (acc[0][0][0] + acc[0][CT - 1][1] + acc[RT - 1][0][2] + acc[RT - 1][CT - 1][3] == 12345.678f && o.f32) o.f32[0] = 1.f;
-        return;
-    }
-#ifdef P2W_GEMM_STAMP
-    const unsigned long long t_loop = p2w_stamp();
-    const EpiArgs ep2 = {ep.bias, ep.sc0, ep.sh0, nullptr, nullptr, ep.residual, ep.ldr, ep.relu0, ep.relu1, ep.relu2, ep.relu_final};
-    gemm_epilogue_dispatch<PREC, RT, CT>(acc, ep2, wscale, m0 + wr * 32 * RT, n0 + wc * 32 * CT, lane, M, N, o, ef);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long t_end = p2w_stamp();
-    // stamp buffer = ep.sh1 (the diagnostic launch passes it there; the sc1 stage is never applied in this build)
-    if (lane == 0 && (wave == 0 || wave == NW / 2) && blockIdx.x < 1024) {
-        unsigned long long* sb = reinterpret_cast<unsigned long long*>(const_cast<float*>(ep.sh1)) + (blockIdx.x * 2 + (wave ? 1 : 0)) * 8;
-        sb[0] = t_loop - t_start; sb[1] = t_wait; sb[2] = t_end - t_loop; sb[3] = t_rd; sb[4] = t_start; sb[5] = t_end;
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        sb[6] = xcc; sb[7] = (unsigned long long)nslab;
-    }
-#else
-    gemm_epilogue_dispatch<PREC, RT, CT>(acc, ep, wscale, m0 + wr * 32 * RT, n0 + wc * 32 * CT, lane, M, N, o, ef);
-#endif
-}
-
-// ------------------------------------------------------------------------------------------------
-// gemm_hp_kernel: the production form of the GEMM above - the same stage image, DMA pieces, fragment reads, MFMAs and
-// epilogue, run by PERSISTENT workgroups.  Workgroup b walks the virtual blocks b, b + gridDim, ... of the XCD-aware tile
+// LDS image of a stage: rows of 128 B = 8 chunks of 16 B, A rows 0..BM-1 then B rows.  Chunk c of a row (c>>2 = plane:
+// hi / lo, or the k half of a single-plane slab; c&3 = 8 k each) is stored at chunk position c ^ ((row >> 1) & 7), so a
+// ds_read_b128 of one chunk index by 16 different rows spreads over all 16 slots of the 256-byte bank row: conflict-free.
+// A DMA piece (one wave-instruction, 1 KiB) = 8 image rows: lane L -> row 8g + (L >> 3), stored chunk L & 7, reading the
+// source chunk (L & 7) ^ swizzle: 8 rows x 128 contiguous bytes = 8 whole cache lines per piece.
+// DMA issue.  8-wave tiles (HALF): waves 0..3 issue the whole stage behind the barrier while waves 4..7 - their SIMD
+// partners, which the hardware's oldest-first arbitration makes the losers of every slab (in-kernel stamps: wave 0 waits
+// 39 % of the loop at the barrier, wave 4 4 %) - start on the MFMAs at once: the issue time of one half is the other half's
+// uncontested MFMA time.  4-wave tiles: every wave spreads its pieces over the first half of the slab's MFMAs instead of
+// issuing them as one burst behind the barrier: a piece costs ~60-180 issue cycles, and with every wave of the workgroup
+// re-aligned by the barrier a burst leaves all four MFMA pipes idle for ~1000 cycles of a ~3000-cycle slab.
+//
+// gemm_hp_kernel runs it on PERSISTENT workgroups.  Workgroup b walks the virtual blocks b, b + gridDim, ... of the XCD-aware tile
 // order (gridDim is a multiple of 8, so a workgroup stays on its XCD's tiles), and the K slabs of consecutive tiles form
 // one software pipeline: the first slab of the next tile is issued at the top of the last slab of the current one, so it
 // lands during that slab's MFMAs and the epilogue.  A workgroup per tile paid the first slab's whole latency (~2 us) and a
@@ -869,15 +517,15 @@ __global__ __launch_bounds__(64 * WR * WC, 2) void gemm_h2g_kernel(const _Float1
 // split-major (piece = j * tiles + tile) and dealt to the XCDs in contiguous blocks, so the workgroups that share an L2 run
 // neighbouring tiles over the SAME K range side by side: a slab of A or W fetched by one is an L2 hit for the others (pieces of
 // one tile side by side - the stream-K order - share nothing: measured fabric-bound at 2.2 us per slab instead of 1.1).
-// `nvb` carries the tile count, `stagger` the split count S.
+// `nvb` carries the tile count, `sk_S` the split count S (0 in the other kernels).
 template <int PREC, int WR, int WC, int RT, int CT, bool DOTK, bool SK>
 __device__ __forceinline__ void gemm_hp_body(const _Float16* __restrict__ A, int ldh_a, const _Float16* __restrict__ Wh, float wscale,
                                              int M, int N, int Kpad, int nMt, int nNt, int nvb, const EpiArgs& ep, const OutArgs& o,
-                                             int ef, int tmode, int stagger, float* __restrict__ skws) {
+                                             int ef, int tmode, int sk_S, float* __restrict__ skws) {
     constexpr int KS = HCfg<PREC>::kslab;
     constexpr int BM = 32 * RT * WR, BN = 32 * CT * WC, NW = WR * WC;
     constexpr int A_CH = 8 * BM, STAGE_CH = A_CH + 8 * BN;
-    constexpr bool HALF = NW == 8;                        // 8-wave tile: waves 0..3 issue the whole stage (see gemm_h2g_kernel)
+    constexpr bool HALF = NW == 8;                        // 8-wave tile: waves 0..3 issue the whole stage (DMA issue above)
     constexpr int NWI = HALF ? NW / 2 : NW;
     constexpr int NI = STAGE_CH / 64 / NWI;
     static_assert(STAGE_CH % (64 * NWI) == 0, "stage must split evenly over the issuing waves");
@@ -896,25 +544,21 @@ __device__ __forceinline__ void gemm_hp_body(const _Float16* __restrict__ A, int
     int L = blockIdx.x, mt, nt;
     int sk_s0 = 0, sk_s1 = 0, sk_piece = 0;   // SK: this workgroup's slab range and piece number
     if constexpr (SK) {
-        const int S = stagger, P = nvb * S, per_xcd = (P + 7) >> 3;
+        const int P = nvb * sk_S, per_xcd = (P + 7) >> 3;
         const int w = blockIdx.x >> 3;
         sk_piece = (blockIdx.x & 7) * per_xcd + w;
         if (w >= per_xcd || sk_piece >= P) return;
         const int j = sk_piece / nvb, r = sk_piece - j * nvb;
-        sk_s0 = (int)((long long)j * nslab / S);
-        sk_s1 = (int)((long long)(j + 1) * nslab / S);
-        if (sk_s0 >= sk_s1) return;              // (S <= nslab: never; the fix-up skips empty pieces the same way)
+        sk_s0 = (int)((long long)j * nslab / sk_S);
+        sk_s1 = (int)((long long)(j + 1) * nslab / sk_S);
+        if (sk_s0 >= sk_s1) return;              // (sk_S <= nslab: never; the fix-up skips empty pieces the same way)
         mt = r / nNt; nt = r - mt * nNt;
-    } else {
-        if (stagger > 0 && ((blockIdx.x >> 3) & 1)) {   // start stagger (100 MHz ticks): every other workgroup of an XCD starts late
-            const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-            while (__builtin_amdgcn_s_memrealtime() - t0 < (unsigned long long)stagger) __builtin_amdgcn_s_sleep(16);
-        }
-        if (!next_tile(L, mt, nt)) return;
+    } else if (!next_tile(L, mt, nt)) {
+        return;
     }
 
     const _Float16* src[NI];
-    auto setup_src = [&](int mt_, int nt_) {   // per-lane DMA sources of a tile (LDS image: gemm_h2g_kernel)
+    auto setup_src = [&](int mt_, int nt_) {   // per-lane DMA sources of a tile (LDS image and DMA pieces: see above)
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
             const int g = (wave % NWI) + NWI * i;
@@ -966,7 +610,6 @@ __device__ __forceinline__ void gemm_hp_body(const _Float16* __restrict__ A, int
         constexpr bool LAST = decltype(last_c)::value;
         // s_waitcnt through the builtin (simm16: vmcnt[3:0] | expcnt 7 << 4 | lgkmcnt << 8 | vmcnt[5:4] << 14): unlike an asm
         // statement it also updates the compiler's own scoreboard, so it does not re-wait later for loads that are done
-        // s_waitcnt through the builtin: unlike an asm statement it also updates the compiler's own scoreboard
         asm volatile("" ::: "memory");
         if (landed) __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0) only: this slab's DMA was waited for behind the epilogue
         else __builtin_amdgcn_s_waitcnt(0x0070);          // vmcnt(0) lgkmcnt(0)
@@ -1059,8 +702,8 @@ template <int PREC, int WR, int WC, int RT, int CT, bool DOTK = false>
 __global__ __launch_bounds__(64 * WR * WC, 2) void gemm_hp_kernel(const _Float16* __restrict__ A, int ldh_a,
                                                                const _Float16* __restrict__ Wh, float wscale, int M, int N,
                                                                int Kpad, int nMt, int nNt, int nvb, EpiArgs ep, OutArgs o, int ef,
-                                                               int tmode, int stagger) {
-    gemm_hp_body<PREC, WR, WC, RT, CT, DOTK, false>(A, ldh_a, Wh, wscale, M, N, Kpad, nMt, nNt, nvb, ep, o, ef, tmode, stagger, nullptr);
+                                                               int tmode) {
+    gemm_hp_body<PREC, WR, WC, RT, CT, DOTK, false>(A, ldh_a, Wh, wscale, M, N, Kpad, nMt, nNt, nvb, ep, o, ef, tmode, 0, nullptr);
 }
 
 // 64 x 128 tiles, three workgroups per CU (4 waves of 32 x 64): for the short-K layers (expand, hoists, the FP modules' skip GEMMs:
@@ -1120,7 +763,6 @@ static int32_t launch_gemm_h(const _Float16* Ah, int32_t ldh_a, const _Float16* 
     if (out_h2 && (ldh_o & 7)) return P2W_EINVAL;
     const int hcols = ldh_o < (N + KA - 1) / KA * KA ? ldh_o : (N + KA - 1) / KA * KA;   // outputs + zero pad to the K-slab boundary
     OutArgs o = {out_f32, ldo, out_h2, ldh_o, hcols, dotw, part, ldpart};
-    const int dbg = (flags >> 16) & 0xff;
     // 256x256 tiles halve the L2->LDS bytes per MFMA; they need enough tiles to fill the CUs and a wide N:
     // one 256x256 workgroup per CU is worth it when N has no column padding at that width and the tiles fill >= 78 % of
     // whole rounds of the chip, from 3/4 of one round up (per-launch A/B over the network's GEMMs: 207 tiles on
@@ -1235,12 +877,7 @@ static int32_t launch_gemm_h(const _Float16* Ah, int32_t ldh_a, const _Float16* 
         }
     }
     // epilogue class for the specialised interior-tile path (0 = generic); needs 32-bit element offsets
-#ifdef P2W_GEMM_STAMP
-    const bool use_s1 = false;   // ep.sh1 carries the stamp buffer
-#else
-    const bool use_s1 = ep.sc1 != nullptr;
-#endif
-    int ef = (ep.relu0 ? 1 : 0) | (ep.sc0 ? 2 : 0) | (ep.relu1 ? 4 : 0) | (use_s1 ? 8 : 0) | (ep.relu2 ? 16 : 0) |
+    int ef = (ep.relu0 ? 1 : 0) | (ep.sc0 ? 2 : 0) | (ep.relu1 ? 4 : 0) | (ep.sc1 ? 8 : 0) | (ep.relu2 ? 16 : 0) |
              ((ep.residual || ep.res_h) ? 32 : 0) | (ep.relu_final ? 64 : 0) | (out_f32 ? 128 : 0) | (out_h2 ? 256 : 0) | (dotw ? 512 : 0) |
              (ep.res_h ? 1024 : 0) | (ep.imeta ? 2048 : 0);
     const size_t lim = (size_t)1 << 31;
@@ -1280,24 +917,8 @@ static int32_t launch_gemm_h(const _Float16* Ah, int32_t ldh_a, const _Float16* 
         }
         return t_cols * 10 < t_rows * 9 ? 1 : 0;
     };
-#if defined(P2W_GEMM_STAMP) || defined(P2W_GEMM_ABLATE)   // diagnostic builds: one workgroup per tile, with the probes
-    if (big) {
-        const int nMt = p2w_cdiv(M, 256), nNt2 = Npad / 256;
-        const int tm = pick_mode(nNt2, nMt, 1);
-        gemm_h2g_kernel<PREC, 2, 4, 4, 2><<<tile_grid(nMt, nNt2, tm), 512, 0, stream>>>(
-            Ah, ldh_a, Wp, (size_t)Npad * Kpad, wscale, M, N, Kpad, nMt, nNt2, ep, o, dbg, ef, tm);
-    } else {
-        const int nMt = p2w_cdiv(M, 128), nNt1 = p2w_cdiv(N, 128);
-        const int tm = pick_mode(nNt1, nMt, 2);
-        gemm_h2g_kernel<PREC, 2, 2, 2, 2><<<tile_grid(nMt, nNt1, tm), 256, 0, stream>>>(
-            Ah, ldh_a, Wp, (size_t)Npad * Kpad, wscale, M, N, Kpad, nMt, nNt1, ep, o, dbg, ef, tm);
-    }
-#else
-    (void)dbg;
-    const int stagger = ((flags >> 8) & 63) * 200;             // diagnostic: start stagger in units of 2 us
-    const int gdiv = (flags & (1 << 14)) ? 2 : (flags & (1 << 15)) ? 4 : 1;   // diagnostic: persistent grid on 1/2, 1/4 of the CUs
     auto pgrid = [&](int nvb, int per_cu) {   // persistent grid: whole XCD rounds, at most per_cu workgroups per CU
-        const int cap = n_cu * per_cu / gdiv;
+        const int cap = n_cu * per_cu;
         int g = nvb < cap ? nvb : cap;
         if (g >= 8) g &= ~7;
         return g;
@@ -1313,15 +934,14 @@ static int32_t launch_gemm_h(const _Float16* Ah, int32_t ldh_a, const _Float16* 
     } else if (big) {
         const int nMt = p2w_cdiv(M, 256), nNt2 = Npad / 256;
         const int tm = pick_mode(nNt2, nMt, 1), nvb = tile_grid(nMt, nNt2, tm);
-        if (dotw) gemm_hp_kernel<PREC, 2, 4, 4, 2, true><<<pgrid(nvb, 1), 512, 0, stream>>>(Ah, ldh_a, Wp, wscale, M, N, Kpad, nMt, nNt2, nvb, ep, o, ef, tm, stagger);
-        else gemm_hp_kernel<PREC, 2, 4, 4, 2><<<pgrid(nvb, 1), 512, 0, stream>>>(Ah, ldh_a, Wp, wscale, M, N, Kpad, nMt, nNt2, nvb, ep, o, ef, tm, stagger);
+        if (dotw) gemm_hp_kernel<PREC, 2, 4, 4, 2, true><<<pgrid(nvb, 1), 512, 0, stream>>>(Ah, ldh_a, Wp, wscale, M, N, Kpad, nMt, nNt2, nvb, ep, o, ef, tm);
+        else gemm_hp_kernel<PREC, 2, 4, 4, 2><<<pgrid(nvb, 1), 512, 0, stream>>>(Ah, ldh_a, Wp, wscale, M, N, Kpad, nMt, nNt2, nvb, ep, o, ef, tm);
     } else {
         const int nMt = p2w_cdiv(M, 128), nNt1 = p2w_cdiv(N, 128);
         const int tm = pick_mode(nNt1, nMt, 2), nvb = tile_grid(nMt, nNt1, tm);
-        if (dotw) gemm_hp_kernel<PREC, 2, 2, 2, 2, true><<<pgrid(nvb, 2), 256, 0, stream>>>(Ah, ldh_a, Wp, wscale, M, N, Kpad, nMt, nNt1, nvb, ep, o, ef, tm, stagger);
-        else gemm_hp_kernel<PREC, 2, 2, 2, 2><<<pgrid(nvb, 2), 256, 0, stream>>>(Ah, ldh_a, Wp, wscale, M, N, Kpad, nMt, nNt1, nvb, ep, o, ef, tm, stagger);
+        if (dotw) gemm_hp_kernel<PREC, 2, 2, 2, 2, true><<<pgrid(nvb, 2), 256, 0, stream>>>(Ah, ldh_a, Wp, wscale, M, N, Kpad, nMt, nNt1, nvb, ep, o, ef, tm);
+        else gemm_hp_kernel<PREC, 2, 2, 2, 2><<<pgrid(nvb, 2), 256, 0, stream>>>(Ah, ldh_a, Wp, wscale, M, N, Kpad, nMt, nNt1, nvb, ep, o, ef, tm);
     }
-#endif
     return P2W_LAUNCH_STATUS();
 }
 
@@ -1424,16 +1044,7 @@ __global__ __launch_bounds__(512, 2) void sa_conv16p_kernel(const float* __restr
                                                             int nMt_, int nNt, const float* __restrict__ b2,
                                                             const float* __restrict__ bn_s, const float* __restrict__ bn_t,
                                                             float* __restrict__ out, int ldo, _Float16* __restrict__ out_h2,
-                                                            int ldh, int dbg_, unsigned* __restrict__ range) {
-    // dbg (profiling ablations, -DP2W_SA_ABLATE builds only): 1 no epilogue, 2 no W2 DMA after the first, 4 no MFMA,
-    // 32 layer-1 weights of slab 0 in every slab, 64 fragments always from stage 0, 128 no barrier,
-    // 8 no producer, 16 no P gather
-#ifdef P2W_SA_ABLATE
-    const int dbg = dbg_;
-#else
-    constexpr int dbg = 0;
-    (void)dbg_;
-#endif
+                                                            int ldh, unsigned* __restrict__ range) {
     constexpr int NP = HCfg<PREC>::planes;
     constexpr int WCn = BN / 64, BM = 32 * RT * (8 / WCn), NW = 8, NR = BM / 128;   // NR producer rows per thread
     constexpr int GPT = 32 / G;                                                     // targets per 32-row tile
@@ -1488,10 +1099,7 @@ __global__ __launch_bounds__(512, 2) void sa_conv16p_kernel(const float* __restr
     // same half of the bank row (2-way conflict on every store: SQ_LDS_BANK_CONFLICT 12 - 20 % of the LDS cycles, r5 profiles);
     // with the halves swapped on odd rows they fill one bank row.  The fragment reads (16-lane groups over 64 banks) stay
     // conflict-free: rows {0-3, 12-15, 20-27} of a group still map to 16 distinct 16-byte slots.
-#ifndef P2W_SA_A_SWZ
-#define P2W_SA_A_SWZ 1   // 0: the B image's swizzle for A as well (A/B builds: tools/build_variant.sh)
-#endif
-    auto imgA = [](int row, int chunk) { return (row * RCH + (NP == 2 ? (chunk ^ ((row >> 1) & 7) ^ (P2W_SA_A_SWZ ? ((row & 1) << 2) : 0)) : (chunk ^ ((row >> 2) & 3)))) * 16; };
+    auto imgA = [](int row, int chunk) { return (row * RCH + (NP == 2 ? (chunk ^ ((row >> 1) & 7) ^ ((row & 1) << 2)) : (chunk ^ ((row >> 2) & 3)))) * 16; };
     const int prow = tid >> 2, pq = tid & 3;   // rows prow + 128*u, u < NR (the swizzle term is the same for all of them)
     const int a_dst = imgA(prow, pq);          // hi plane chunk; the lo chunk (f16x3) is at a_dst ^ 64
     // per-lane pieces of the B DMA source that do not depend on the item
@@ -1563,26 +1171,13 @@ __global__ __launch_bounds__(512, 2) void sa_conv16p_kernel(const float* __restr
             const float4 wx = wr_.w[half][0], wy = wr_.w[half][1], wz = wr_.w[half][2], wf = wr_.w[half][3];
             const float4 p = src.v[u][half];
             const float gx = rg.x, gy = rg.y, gz = rg.z, gw = rg.w;
+            // scalar FMAs: as packed v_pk_fma_f32 pairs (the same bits) they measured +3 % on the class (1.88 against 1.82 ms): the
+            // packed form issues no faster and co-executes worse with the MFMAs
             float v[4];
-#if P2W_SA_PK_FMA
-            // the four FMAs of a column pair as two-wide packed ones (v_pk_fma_f32: the same IEEE fma per half, so the same bits; half
-            // the VALU issue slots of the producer's arithmetic)
-            const fpair gxx = {gx, gx}, gyy = {gy, gy}, gzz = {gz, gz}, gww = {gw, gw};
-            fpair a01 = __builtin_elementwise_fma(gxx, fpair{wx.x, wx.y}, fpair{p.x, p.y});
-            fpair a23 = __builtin_elementwise_fma(gxx, fpair{wx.z, wx.w}, fpair{p.z, p.w});
-            a01 = __builtin_elementwise_fma(gyy, fpair{wy.x, wy.y}, a01);
-            a23 = __builtin_elementwise_fma(gyy, fpair{wy.z, wy.w}, a23);
-            a01 = __builtin_elementwise_fma(gzz, fpair{wz.x, wz.y}, a01);
-            a23 = __builtin_elementwise_fma(gzz, fpair{wz.z, wz.w}, a23);
-            a01 = __builtin_elementwise_fma(gww, fpair{wf.x, wf.y}, a01);
-            a23 = __builtin_elementwise_fma(gww, fpair{wf.z, wf.w}, a23);
-            v[0] = fmaxf(a01[0], 0.f); v[1] = fmaxf(a01[1], 0.f); v[2] = fmaxf(a23[0], 0.f); v[3] = fmaxf(a23[1], 0.f);
-#else
             v[0] = fmaxf(fmaf(gw, wf.x, fmaf(gz, wz.x, fmaf(gy, wy.x, fmaf(gx, wx.x, p.x)))), 0.f);
             v[1] = fmaxf(fmaf(gw, wf.y, fmaf(gz, wz.y, fmaf(gy, wy.y, fmaf(gx, wx.y, p.y)))), 0.f);
             v[2] = fmaxf(fmaf(gw, wf.z, fmaf(gz, wz.z, fmaf(gy, wy.z, fmaf(gx, wx.z, p.z)))), 0.f);
             v[3] = fmaxf(fmaf(gw, wf.w, fmaf(gz, wz.w, fmaf(gy, wy.w, fmaf(gx, wx.w, p.w)))), 0.f);
-#endif
             if constexpr (PREC == 0) {
                 unsigned h01, l01, h23, l23;
                 split_pair(v[0], v[1], h01, l01);
@@ -1683,42 +1278,30 @@ __global__ __launch_bounds__(512, 2) void sa_conv16p_kernel(const float* __restr
     Degs dg_;
     load_deg(c0.mt, dg_);   // item 0; later items' counts arrive one iteration ahead (dg_n)
     float amax = 0.f;       // range watch: max |output| of this wave's items, committed once at the end
-#ifdef P2W_SA_STAMP
-    unsigned long long t_wait = 0, t_epi = 0, t_mma = 0, t_ld = 0;
-    const unsigned long long t_start = p2w_stamp();
-#endif
     for (int g = 0; g < total; ++g) {
-#ifdef P2W_SA_STAMP
-        const unsigned long long t_a = p2w_stamp();
-#endif
         // B(g) landed (waited for in front of the previous iteration's epilogue, see there), A(g) written, stage (g+1)&1 free.
         // No __syncthreads(): its fence would wait (vmcnt(0)) for the stores of an epilogue issued a moment ago.
         asm volatile("" ::: "memory");
         __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): the producer's asm ds_writes of A(g) (see produce)
-        if (!(dbg & 128)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-#ifdef P2W_SA_STAMP
-        const unsigned long long t_b = p2w_stamp();
-        t_wait += t_b - t_a;
-#endif
         // All register loads of the iteration go out HERE, before the DMA: the gather of slab g+2 (into `vb`: the producer
         // still needs `va`), the metadata of slab g+3 and the epilogue parameters of slab g+1's item.  Nothing reads them
         // before the rotation at the end of the iteration, so the only wait on them sits in front of the next barrier.
         Vals vb;
-        if (!(dbg & 16)) gather(mb, k_of(c2), vb); else vb = va;
+        gather(mb, k_of(c2), vb);
         meta_of(c3, mc);
         Degs dg_n;
         load_deg(c1.mt, dg_n);
         WRegs wk;
-        if (!(dbg & 32)) load_w(k_of(c1), wk); else load_w(0, wk);   // (ablation 32: loop-invariant, hoisted by the compiler)
+        load_w(k_of(c1), wk);
         __builtin_amdgcn_sched_barrier(0);
-        if (g + 1 < total && !(dbg & 2))
+        if (g + 1 < total)
             issue((g + 1) & 1, W2h + (size_t)c1.nt * BN * NP * C1pad, c1.s * H_BK);
-        const char* st = S + (size_t)((dbg & 64) ? 0 : (g & 1)) * STAGE_CH * 16;   // (ablation 64: see the fragment reads)
-#if P2W_SA_PREFETCH_FRAGS
+        const char* st = S + (size_t)(g & 1) * STAGE_CH * 16;
         // both k steps' fragments are requested up front (the kernel has the registers: 212 of 256): the second step's reads
         // would otherwise sit behind the sched_barrier that closes the first step's producer interleave, i.e. be issued when
-        // their values are needed
+        // their values are needed (A/B against reading each step's fragments at its start: fused PointNetConv class -2.9 %)
         h8 afq[2][NP][RT], bfq[2][NP][2];
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
@@ -1729,64 +1312,31 @@ __global__ __launch_bounds__(512, 2) void sa_conv16p_kernel(const float* __restr
 #pragma unroll
                 for (int t = 0; t < 2; ++t) bfq[kk][p][t] = *reinterpret_cast<const h8*>(st + (offB[t] ^ (kk << 5) ^ (p << 6)));
             }
-#endif
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
-#if P2W_SA_PREFETCH_FRAGS
             auto& af = afq[kk];
             auto& bf = bfq[kk];
-#else
-            h8 af[NP][RT], bf[NP][2];
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-#pragma unroll
-                for (int t = 0; t < RT; ++t) af[p][t] = *reinterpret_cast<const h8*>(st + (offA[t] ^ (kk << 5) ^ (p << 6)));
-#pragma unroll
-                for (int t = 0; t < 2; ++t) bf[p][t] = *reinterpret_cast<const h8*>(st + (offB[t] ^ (kk << 5) ^ (p << 6)));
-            }
-#endif
-            if (!(dbg & 4)) {
 #pragma unroll
             for (int i = 0; i < RT; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-#ifdef P2W_SA_MFMA16_TIMING   // timing only (wrong results): two 16x16x32 MFMAs on the same operand registers per 32x32x16
-                    auto t16 = [&](h8 a_, h8 b_) {
-                        f32x4 c0 = {acc[i][j][8 * kk], acc[i][j][8 * kk + 1], acc[i][j][8 * kk + 2], acc[i][j][8 * kk + 3]};
-                        f32x4 c1 = {acc[i][j][8 * kk + 4], acc[i][j][8 * kk + 5], acc[i][j][8 * kk + 6], acc[i][j][8 * kk + 7]};
-                        c0 = h_mfma16<PREC>(a_, b_, c0);
-                        c1 = h_mfma16<PREC>(a_, b_, c1);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) { acc[i][j][8 * kk + e] = c0[e]; acc[i][j][8 * kk + 4 + e] = c1[e]; }
-                    };
-                    if constexpr (PREC == 0) { t16(af[1][i], bf[0][j]); t16(af[0][i], bf[1][j]); }
-                    t16(af[0][i], bf[0][j]);
-#else
                     if constexpr (PREC == 0) {
                         acc[i][j] = h_mfma<PREC>(af[1][i], bf[0][j], acc[i][j]);
                         acc[i][j] = h_mfma<PREC>(af[0][i], bf[1][j], acc[i][j]);
                     }
                     acc[i][j] = h_mfma<PREC>(af[0][i], bf[0][j], acc[i][j]);
-#endif
                 }
-            }
-            if (kk == 0) {
-                if (!(dbg & 8)) {   // producer VALU work is interleaved into the gaps of the MFMAs above
-                    produce((g + 1) & 1, ma, k_of(c1), va, wk);   // unconditional: after the last slab it fills a stage nobody reads
-                    constexpr int NM = 2 * RT * (PREC == 0 ? 3 : 1);   // MFMAs of this half slab
+            if (kk == 0) {   // producer VALU work is interleaved into the gaps of the MFMAs above
+                produce((g + 1) & 1, ma, k_of(c1), va, wk);   // unconditional: after the last slab it fills a stage nobody reads
+                constexpr int NM = 2 * RT * (PREC == 0 ? 3 : 1);   // MFMAs of this half slab
 #pragma unroll
-                    for (int q = 0; q < NM; ++q) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
-                        __builtin_amdgcn_sched_group_barrier(0x002, (PREC == 0 ? 16 : 40) * NR / RT, 0);   // VALU
-                    }
+                for (int q = 0; q < NM; ++q) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
+                    __builtin_amdgcn_sched_group_barrier(0x002, (PREC == 0 ? 16 : 40) * NR / RT, 0);   // VALU
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-#ifdef P2W_SA_STAMP
-        const unsigned long long t_c = p2w_stamp();
-        t_mma += t_c - t_b;            // DMA issue + fragment reads + MFMAs + producer + gather issue
-#endif
         // Everything this iteration loaded (gather of slab g+2, metadata of slab g+3, next item's degrees) and the W2 DMA of slab
         // g+1 is waited for HERE, by an opaque use of the loaded registers: in front of the epilogue's stores, which then stay in
         // flight across the next barrier (loads, stores and LDS-DMA retire through one counter: a wait placed behind the
@@ -1802,23 +1352,18 @@ __global__ __launch_bounds__(512, 2) void sa_conv16p_kernel(const float* __restr
 #pragma unroll
             for (int q = 0; q < GPT; ++q) asm volatile("" : "+v"(dg_n.d[i][q]));
         __builtin_amdgcn_s_waitcnt(p2w_vmcnt_imm(0));   // ... and the DMA (the compiler's own wait above normally is vmcnt(0) already)
-#ifdef P2W_SA_STAMP
-        t_ld += p2w_stamp() - t_c;     // the wait for the iteration's loads and the DMA alone
-#endif
         if (c0.s == nslab - 1) {  // item finished: reduce over neighbour slots and store, then start the next accumulation
-            if (!(dbg & 1)) {
-                SaEpiRegs<RT, GPT> e;
+            SaEpiRegs<RT, GPT> e;
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const int col = min(c0.nt * BN + wc * 64 + j * 32 + (lane & 31), C2 - 1);
-                    e.bias[j] = Ep[col]; e.s[j] = Ep[SA_EPI_COLS + col]; e.t[j] = Ep[2 * SA_EPI_COLS + col];
-                }
-#pragma unroll
-                for (int i = 0; i < RT; ++i)
-#pragma unroll
-                    for (int q = 0; q < GPT; ++q) e.dsc[i][q] = (c0.mt * (BM / 32) + wr * RT + i >= M) ? -1 : dg_.d[i][q];
-                sa_epilogue_regs<PREC, RT, G>(acc, wscale, c0.nt * BN, wc, lane, e, C2, out, ldo, out_h2, ldh, amax);
+            for (int j = 0; j < 2; ++j) {
+                const int col = min(c0.nt * BN + wc * 64 + j * 32 + (lane & 31), C2 - 1);
+                e.bias[j] = Ep[col]; e.s[j] = Ep[SA_EPI_COLS + col]; e.t[j] = Ep[2 * SA_EPI_COLS + col];
             }
+#pragma unroll
+            for (int i = 0; i < RT; ++i)
+#pragma unroll
+                for (int q = 0; q < GPT; ++q) e.dsc[i][q] = (c0.mt * (BM / 32) + wr * RT + i >= M) ? -1 : dg_.d[i][q];
+            sa_epilogue_regs<PREC, RT, G>(acc, wscale, c0.nt * BN, wc, lane, e, C2, out, ldo, out_h2, ldh, amax);
 #pragma unroll
             for (int i = 0; i < RT; ++i)
 #pragma unroll
@@ -1826,20 +1371,11 @@ __global__ __launch_bounds__(512, 2) void sa_conv16p_kernel(const float* __restr
 #pragma unroll
                     for (int e2 = 0; e2 < 16; ++e2) acc[i][j][e2] = 0.f;
         }
-#ifdef P2W_SA_STAMP
-        t_epi += p2w_stamp() - t_c;
-#endif
         __builtin_amdgcn_sched_barrier(0);
         va = vb; ma = mb; mb = mc; dg_ = dg_n;
         c0 = c1; c1 = c2; c2 = c3; c3 = nxt(c3);
     }
     if (range) range_commit_max(range, amax, lane);
-#ifdef P2W_SA_STAMP
-    if (lane == 0 && (wave == 0 || wave == 4) && blockIdx.x < 256) {   // stamp buffer: the 64 KiB behind the tile descriptors
-        unsigned long long* sb = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(const_cast<int*>(desc) + (size_t)M * GPT) + 64) + (blockIdx.x * 2 + (wave ? 1 : 0)) * 8;
-        sb[0] = p2w_stamp() - t_start; sb[1] = t_wait; sb[2] = t_epi; sb[3] = t_mma; sb[4] = (unsigned long long)total; sb[5] = (unsigned long long)my_items; sb[6] = t_ld;
-    }
-#endif
 }
 
 
@@ -1882,7 +1418,6 @@ static int32_t launch_sa_conv_h(const float* P, int32_t ldp, int32_t n_src, cons
     const int n_cu = p2w_cu_count();
     // 256-column items halve the A production per output column; measured on levels 2 / 3 (C2 = 256 / 512): 2.73 vs 2.82-2.97 ms
     const bool wide = (flags & (P2W_SA_ITEM_256 | P2W_SA_ITEM_128)) ? (flags & P2W_SA_ITEM_256) != 0 : C2 > 128;
-    const int sadbg = (flags >> 16) & 0xff;
     const int tpi = wide ? 4 : 8, nNt3 = p2w_cdiv(C2, wide ? 256 : 128);   // tiles per work item, column tiles
     const float4* x4 = reinterpret_cast<const float4*>(xyzr_src);
     // one class of targets: metadata pre-pass over `rows_max` rows + the persistent kernel over at most `tiles_max` tiles
@@ -1901,11 +1436,11 @@ static int32_t launch_sa_conv_h(const float* P, int32_t ldp, int32_t n_src, cons
         if (wide)
             sa_conv16p_kernel<PREC, 256, 2, G><<<grid, 512, 0, stream>>>(
                 P, ldp, meta_j, meta_g, desc, tiles_dev, (int)tiles_max, w1r4, C1, C1pad, W2h, (size_t)C2pad * C1pad, wscale, C2, nMt3,
-                nNt3, b2, bn_s, bn_t, out, ldo, out_h2, ldh, sadbg, range);
+                nNt3, b2, bn_s, bn_t, out, ldo, out_h2, ldh, range);
         else
             sa_conv16p_kernel<PREC, 128, 2, G><<<grid, 512, 0, stream>>>(
                 P, ldp, meta_j, meta_g, desc, tiles_dev, (int)tiles_max, w1r4, C1, C1pad, W2h, (size_t)C2pad * C1pad, wscale, C2, nMt3,
-                nNt3, b2, bn_s, bn_t, out, ldo, out_h2, ldh, sadbg, range);
+                nNt3, b2, bn_s, bn_t, out, ldo, out_h2, ldh, range);
     };
     char* w = static_cast<char*>(ws);
     if (!(flags & P2W_SA_PACK8)) {

@@ -593,6 +593,14 @@ def test_hot_kernels_stay_off_the_register_cliff():
             assert v["VGPRs Spill"] == 0, (k, v)
 
 
+def test_feature_kernels_have_no_build_switches():
+    """The GEMM and PointNetConv sources compile to one program: no -D (P2W_EXTRA_CFLAGS) can change what they build."""
+    for src in ("p2w_hgemm.h", "p2w_feat.hip", "p2w_feat_h1.hip"):
+        text = open(os.path.join(ROOT, "pointstowood_amd", "csrc", src)).read()
+        hits = re.findall(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b.*\bP2W_\w+", text, re.M)
+        assert not hits, (src, hits)
+
+
 def test_pick_chunk_properties():
     from pointstowood_amd.engine import pick_chunk
     rounds = lambda rows, t: -(-(-(-rows // 256) * t) // 256)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The FP modules' launches of one sequential bench forward under a variant library (tools/build_variant.sh NAME
-"-DP2W_INTERP_DEPTH=n" feat) and an fp_hoist threshold: per-launch HIP-event times (median of 7) of the gemm_mlp class and the
+"""The FP modules' launches of one sequential bench forward under a given library (e.g. a variant from tools/build_variant.sh)
+and an fp_hoist threshold: per-launch HIP-event times (median of 7) of the gemm_mlp class and the
 interpolation class.   python tools/interp_epi_ab.py [lib.so] [key=value ...]"""
 import os, statistics, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
