@@ -33,15 +33,10 @@ def main(argv=None):
     path = args.input_file
     if os.path.splitext(path)[1].lower() != ".ply":
         raise SystemExit(f"{path}: only .ply input is built (the reference also reads .las / .pcd through laspy / its own parser)")
-    import torch
     from pointstowood_amd import io
     from pointstowood_amd.cluster import euclidean_cluster
 
-    cols = io.read_ply(path)
-    for c in ("x", "y", "z"):
-        if c not in cols:
-            raise SystemExit(f"{path}: no '{c}' column")
-    xyz = torch.from_numpy(np.stack([cols[c].astype(np.float64) for c in ("x", "y", "z")], axis=1)).to("cuda")
+    cols, xyz = io.read_ply_points(path)
     labels, n_clusters = euclidean_cluster(xyz, args.cluster_tolerance, args.min_cluster_size, args.max_cluster_size)
     labels = labels.cpu().numpy()
     print(f"Number of clusters: {n_clusters}")

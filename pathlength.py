@@ -39,15 +39,10 @@ def file_list(args):
 
 
 def process(path, args):
-    import torch
     from pointstowood_amd import io
     from pointstowood_amd.pathlength import downsample, path_length
 
-    cols = io.read_ply(path)
-    for c in ("x", "y", "z"):
-        if c not in cols:
-            raise SystemExit(f"{path}: no '{c}' column")
-    xyz = torch.from_numpy(np.stack([cols[c].astype(np.float64) for c in ("x", "y", "z")], axis=1)).to("cuda")
+    cols, xyz = io.read_ply_points(path)
     if args.downsample > 0:
         reps, owner = downsample(xyz, args.downsample)
         sub = xyz[reps].contiguous()

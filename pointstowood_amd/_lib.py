@@ -152,6 +152,22 @@ def stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def stage_timer(on: bool):
+    """(mark, ms) of a ``stats=`` run: ``mark()`` records an event on the current stream (nothing when ``on`` is false), ``ms()``
+    waits for the last one and returns the GPU milliseconds between consecutive marks."""
+    events = []
+
+    def mark():
+        if on:
+            events.append(torch.cuda.Event(enable_timing=True))
+            events[-1].record()
+
+    def ms():
+        events[-1].synchronize()
+        return [a.elapsed_time(b) for a, b in zip(events[:-1], events[1:])]
+    return mark, ms
+
+
 def require_cuda(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:

@@ -3,9 +3,9 @@
 Reference: ``PointCloudClassifier`` (``pointstowood/src/predicter.py:107-142``): a KD-tree (pykdtree, CPU) over ALL
 classified points (every voxel of every grid size, so most plot points occur several times), each original point takes
 its k = 64 (``any_wood == 1``) or 32 nearest classified points, ``pwood`` = median of their probabilities and the label
-by the weighted vote / any-wood rule (numba).  Here: the classified points are sorted once into a uniform cell grid
-(``p2w_voxel_sample``'s order / keys / grid), the queries into Morton order of the same grid, and the grid-indexed exact
-kNN (``p2w_knn_grid`` with ``P2W_SEARCH_BOX``) runs in fp32 on coordinates made local to the cloud.  The reference's tree
+by the weighted vote / any-wood rule (numba).  Here: the classified points are sorted once into the plot's cell grid
+(``plotgrid.build``: ``p2w_voxel_sample``'s order / keys / grid), the queries into Morton order of the same grid, and the
+grid-indexed exact kNN (``p2w_knn_grid`` with ``P2W_SEARCH_BOX``) runs in fp32 on coordinates made local to the cloud.  The reference's tree
 measures in float64 on the un-shifted coordinates (``predicter.py:205`` makes ``classified_pc`` float64, pykdtree keeps the
 data's type), so ``p2w_knn_refine_f64`` then re-ranks every query's neighbourhood in float64 on the coordinates as given:
 the fp32 result bounds the k-th distance, every candidate inside that bound is measured exactly, the k nearest by
@@ -16,14 +16,8 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
+from . import _lib, plotgrid
 from ._lib import SEARCH_BOX, SEARCH_X_INDEX_IN_W, check, lib, ptr
-
-
-def _records(xyz: torch.Tensor) -> torch.Tensor:
-    out = torch.zeros((xyz.shape[0], 4), dtype=torch.float32, device=xyz.device)
-    out[:, :3] = xyz
-    return out
 
 
 def auto_cell(cls_xyz: torch.Tensor, k: int) -> float:
@@ -46,50 +40,20 @@ def neighbours(cls_xyz: torch.Tensor, query_xyz: torch.Tensor, k: int, cell: flo
     L, dev = lib(), cls_xyz.device
     nc, nq = cls_xyz.shape[0], query_xyz.shape[0]
     i32 = dict(dtype=torch.int32, device=dev)
-    cls64 = cls_xyz.to(torch.float64)
-    origin = cls64.min(dim=0).values                       # the fp32 search runs on coordinates local to the cloud
-    cls32 = (cls64 - origin).to(torch.float32)
-    if cell is None:
-        cell = auto_cell(cls32, k)
-    cand = _records(cls32)
-    del cls32
+    g = plotgrid.build(cls_xyz, cell if cell is not None else (lambda loc: auto_cell(loc.to(torch.float32), k)), table_cells,
+                       sorted_records=True)
     ptr_c = torch.tensor([0, nc], **i32)
-    order = torch.empty(nc, **i32)
-    skeys = torch.empty(nc, dtype=torch.int64, device=dev)
-    grid = torch.zeros(8, dtype=torch.int64, device=dev)
-    ws = torch.empty(int(L.p2w_voxel_sample_ws_bytes(max(nc, 1))), dtype=torch.uint8, device=dev)
-    idx, ptr_out, batch_out = torch.empty(nc, **i32), torch.empty(2, **i32), torch.empty(nc, **i32)
-    check(L.p2w_voxel_sample(ptr(cand), ptr(ptr_c), 1, nc, float(cell), ptr(idx), ptr(ptr_out), ptr(batch_out), ptr(order),
-                             ptr(skeys), None, ptr(grid), None, None, ptr(ws), ws.numel(), _lib.stream()), "voxel_sample")
-    del idx, batch_out, ws
-    rec_c = torch.empty((nc, 4), dtype=torch.float32, device=dev)
-    check(L.p2w_index_records(ptr(cand), ptr(order), ptr(ptr_c), 1, nc, ptr(rec_c), _lib.stream()), "index_records")
-    del cand
-    order64 = order.long()
-    cs64 = cls64[order64].contiguous()                     # float64 candidates in the grid's cell-sorted order
-    del cls64
     pos_of = torch.empty(nc, **i32)
-    pos_of[order64] = torch.arange(nc, **i32)
-    del order64
+    pos_of[g.order.long()] = torch.arange(nc, **i32)
     q64 = query_xyz.to(torch.float64)
-    qrec = _records((q64 - origin).to(torch.float32))
+    qrec = plotgrid.records(q64 - g.origin)
     qorder = torch.empty(nq, **i32)
     ws = torch.empty(int(L.p2w_morton_order_ws_bytes(max(nq, 1))), dtype=torch.uint8, device=dev)
-    check(L.p2w_morton_order(ptr(qrec), nq, ptr(grid), ptr(qorder), ptr(ws), ws.numel(), _lib.stream()), "morton_order")
+    check(L.p2w_morton_order(ptr(qrec), nq, ptr(g.grid), ptr(qorder), ptr(ws), ws.numel(), _lib.stream()), "morton_order")
     del ws
     qsorted = qrec[qorder.long()].contiguous()
     del qrec
-    # cell -> first-candidate table of the plot's grid (one load per search run instead of a bisection of the 10^7 keys); the
-    # grid's size is read back once - a plot whose grid would not fit `table_cells` entries is searched by bisection
-    dims = grid.cpu()[4:7].tolist()
-    ox, oy, oz = origin.cpu().tolist()
-    n_cells = int(dims[0]) * int(dims[1]) * int(dims[2])
-    cell_start = None
-    if 0 < n_cells <= int(table_cells):
-        cell_start = torch.empty(n_cells + 1, **i32)
-        ws = torch.empty(int(L.p2w_cell_starts_ws_bytes(n_cells)) + 256, dtype=torch.uint8, device=dev)
-        check(L.p2w_cell_starts(ptr(skeys), nc, n_cells, ptr(cell_start), ptr(ws), ws.numel(), _lib.stream()), "cell_starts")
-        del ws
+    ox, oy, oz = g.origin.cpu().tolist()
     for s in range(0, nq, chunk):
         m = min(chunk, nq - s)
         q = qsorted[s:s + m]
@@ -97,12 +61,43 @@ def neighbours(cls_xyz: torch.Tensor, query_xyz: torch.Tensor, k: int, cell: flo
         ptr_q = torch.tensor([0, m], **i32)
         nbr = torch.empty((m, k), **i32)
         deg = torch.empty(m, **i32)
-        check(L.p2w_knn_grid_indexed(ptr(rec_c), ptr(skeys), ptr(ptr_c), ptr(grid), ptr(cell_start), ptr(q), None, ptr(ptr_q), 1, m, k,
-                                     ptr(nbr), ptr(deg), None, SEARCH_X_INDEX_IN_W | SEARCH_BOX, _lib.stream()), "knn_grid")
+        check(L.p2w_knn_grid_indexed(ptr(g.records_sorted), ptr(g.keys), ptr(ptr_c), ptr(g.grid), ptr(g.cell_start), ptr(q), None,
+                                     ptr(ptr_q), 1, m, k, ptr(nbr), ptr(deg), None, SEARCH_X_INDEX_IN_W | SEARCH_BOX, _lib.stream()),
+              "knn_grid")
         qs64 = q64[rows].contiguous()
-        check(L.p2w_knn_refine_f64(ptr(cs64), ptr(order), ptr(pos_of), ptr(skeys), ptr(cell_start), ptr(grid), ox, oy, oz, ptr(qs64),
-                                   m, nc, k, ptr(nbr), ptr(deg), _lib.stream()), "knn_refine_f64")
+        check(L.p2w_knn_refine_f64(ptr(g.xyz_sorted), ptr(g.order), ptr(pos_of), ptr(g.keys), ptr(g.cell_start), ptr(g.grid), ox, oy, oz,
+                                   ptr(qs64), m, nc, k, ptr(nbr), ptr(deg), _lib.stream()), "knn_refine_f64")
         yield rows, nbr, deg
+
+
+def _collect(cls_xyz, cls_pred, cls_prob, query_xyz, any_wood, cell, chunk, kth: bool):
+    """(label, pwood, dk): ``dk`` [nq] float64 = the distance to the k-th neighbour (+inf where fewer than k exist) when ``kth``."""
+    L = lib()
+    k = 32 if any_wood != 1 else 64
+    nq, dev = query_xyz.shape[0], query_xyz.device
+    pred = cls_pred.to(torch.float32).contiguous()
+    prob = cls_prob.to(torch.float32).contiguous()
+    label = torch.zeros(nq, dtype=torch.float32, device=dev)
+    pwood = torch.zeros(nq, dtype=torch.float32, device=dev)
+    dk = torch.full((nq,), float("inf"), dtype=torch.float64, device=dev) if kth else None
+    if cls_xyz.shape[0] == 0 or nq == 0:
+        return label, pwood, dk
+    if kth:
+        c64, q64 = cls_xyz.to(torch.float64), query_xyz.to(torch.float64)
+    for rows, nbr, deg in neighbours(cls_xyz, query_xyz, k, cell, chunk):
+        m = rows.shape[0]
+        lab = torch.empty(m, dtype=torch.float32, device=dev)
+        pw = torch.empty(m, dtype=torch.float32, device=dev)
+        check(L.p2w_vote(ptr(nbr), ptr(deg), k, ptr(pred), ptr(prob), m, float(any_wood), ptr(lab), ptr(pw), _lib.stream()),
+              "vote")
+        label[rows] = lab
+        pwood[rows] = pw
+        if kth:
+            full = deg >= k
+            last = nbr[:, k - 1].long().clamp(min=0)
+            d = (c64[last] - q64[rows]).pow(2).sum(dim=1).sqrt()
+            dk[rows] = torch.where(full, d, torch.full_like(d, float("inf")))
+    return label, pwood, dk
 
 
 def collect_predictions(cls_xyz, cls_pred, cls_prob, query_xyz, any_wood: float = 1.0, cell: float | None = None,
@@ -112,24 +107,7 @@ def collect_predictions(cls_xyz, cls_pred, cls_prob, query_xyz, any_wood: float 
     cls_xyz [nc,3], cls_pred [nc] (0/1), cls_prob [nc]: the classified points; query_xyz [nq,3]: the original points
     (float32 or float64; neighbours are the float64 KD-tree's, see ``neighbours``).
     k = 64 when ``any_wood == 1`` else 32 (predicter.py:137)."""
-    L = lib()
-    k = 32 if any_wood != 1 else 64
-    nq, dev = query_xyz.shape[0], query_xyz.device
-    pred = cls_pred.to(torch.float32).contiguous()
-    prob = cls_prob.to(torch.float32).contiguous()
-    label = torch.zeros(nq, dtype=torch.float32, device=dev)
-    pwood = torch.zeros(nq, dtype=torch.float32, device=dev)
-    if cls_xyz.shape[0] == 0 or nq == 0:
-        return label, pwood
-    for rows, nbr, deg in neighbours(cls_xyz, query_xyz, k, cell, chunk):
-        m = rows.shape[0]
-        lab = torch.empty(m, dtype=torch.float32, device=dev)
-        pw = torch.empty(m, dtype=torch.float32, device=dev)
-        check(L.p2w_vote(ptr(nbr), ptr(deg), k, ptr(pred), ptr(prob), m, float(any_wood), ptr(lab), ptr(pw), _lib.stream()),
-              "vote")
-        label[rows] = lab
-        pwood[rows] = pw
-    return label, pwood
+    return _collect(cls_xyz, cls_pred, cls_prob, query_xyz, any_wood, cell, chunk, False)[:2]
 
 
 def collect_predictions_checked(cls_xyz, cls_pred, cls_prob, query_xyz, any_wood: float = 1.0, cell: float | None = None,
@@ -137,27 +115,4 @@ def collect_predictions_checked(cls_xyz, cls_pred, cls_prob, query_xyz, any_wood
     """``collect_predictions`` plus, per query, the float64 distance to its k-th neighbour among ``cls_xyz`` (+inf where fewer
     than k candidates exist): what a caller that searched a SUBSET of the classified points needs to prove the result exact
     (pipeline._backproject_spatial: every candidate not in the subset lies farther than that distance)."""
-    L = lib()
-    k = 32 if any_wood != 1 else 64
-    nq, dev = query_xyz.shape[0], query_xyz.device
-    pred = cls_pred.to(torch.float32).contiguous()
-    prob = cls_prob.to(torch.float32).contiguous()
-    label = torch.zeros(nq, dtype=torch.float32, device=dev)
-    pwood = torch.zeros(nq, dtype=torch.float32, device=dev)
-    dk = torch.full((nq,), float("inf"), dtype=torch.float64, device=dev)
-    if cls_xyz.shape[0] == 0 or nq == 0:
-        return label, pwood, dk
-    c64, q64 = cls_xyz.to(torch.float64), query_xyz.to(torch.float64)
-    for rows, nbr, deg in neighbours(cls_xyz, query_xyz, k, cell, chunk):
-        m = rows.shape[0]
-        lab = torch.empty(m, dtype=torch.float32, device=dev)
-        pw = torch.empty(m, dtype=torch.float32, device=dev)
-        check(L.p2w_vote(ptr(nbr), ptr(deg), k, ptr(pred), ptr(prob), m, float(any_wood), ptr(lab), ptr(pw), _lib.stream()),
-              "vote")
-        label[rows] = lab
-        pwood[rows] = pw
-        full = deg >= k
-        last = nbr[:, k - 1].long().clamp(min=0)
-        d = (c64[last] - q64[rows]).pow(2).sum(dim=1).sqrt()
-        dk[rows] = torch.where(full, d, torch.full_like(d, float("inf")))
-    return label, pwood, dk
+    return _collect(cls_xyz, cls_pred, cls_prob, query_xyz, any_wood, cell, chunk, True)

@@ -19,7 +19,7 @@
 // and every older parent is still an ancestor, so such a value only lengthens a walk; a hook on a stale root fails, and the
 // value its CAS returns (the true parent) is where the walk continues.  No workgroup waits for another: a failed CAS means
 // another hook succeeded.
-#include "p2w_common.h"
+#include "p2w_cells.h"
 
 namespace {            // the hand-written device-wide exclusive scan (p2w_sort.h), with internal linkage in this translation unit
 #include "p2w_sort.h"
@@ -27,7 +27,6 @@ namespace {            // the hand-written device-wide exclusive scan (p2w_sort.
 
 namespace {
 
-__device__ __forceinline__ int ec_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ bool ec_cas(int* p, int& expected, int desired) {
     return __hip_atomic_compare_exchange_strong(p, &expected, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -35,9 +34,9 @@ __device__ __forceinline__ bool ec_cas(int* p, int& expected, int desired) {
 // an ancestor of x that was a root when its parent word was read; halves the path on the way (parent[x] -> grandparent, by CAS)
 __device__ __forceinline__ int ec_find(int* parent, int x) {
     while (true) {
-        const int p = ec_load(parent + x);
+        const int p = cells_load(parent + x);
         if (p == x) return x;
-        const int gp = ec_load(parent + p);
+        const int gp = cells_load(parent + p);
         if (gp == p) return p;
         int e = p;
         ec_cas(parent + x, e, gp);                 // (fails harmlessly when another thread moved parent[x] first)
@@ -58,14 +57,6 @@ __device__ __forceinline__ int ec_unite(int* parent, int a, int b) {
     }
 }
 
-__device__ __forceinline__ int ec_lower_bound(const unsigned long long* __restrict__ keys, int lo, int hi, unsigned long long key) {
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (keys[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(256) void ec_init_kernel(int n, int* __restrict__ parent, int* __restrict__ size) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -80,12 +71,12 @@ __global__ __launch_bounds__(256) void ec_link_kernel(const double* __restrict__
     const int p = blockIdx.x * 256 + threadIdx.x;
     unsigned long long evaluated = 0;
     if (p < n) {
-        const long long d0 = gridp->dims[0], d1 = gridp->dims[1], d2 = gridp->dims[2];
-        const long long key = (long long)keys[p];
-        const long long cx = key % d0, cy = (key / d0) % d1, cz = key / (d0 * d1);
+        const CellGrid g{keys, cell_start, n, gridp->dims[0], gridp->dims[1], gridp->dims[2]};
+        const long long d0 = g.d0, d1 = g.d1, d2 = g.d2;
+        long long cx, cy, cz;
+        g.coords((long long)keys[p], cx, cy, cz);
         const long long xlo = cx > 0 ? cx - 1 : 0, xhi = cx + 1 < d0 ? cx + 1 : cx;
         const double px = cs[3 * (size_t)p], py = cs[3 * (size_t)p + 1], pz = cs[3 * (size_t)p + 2];
-        auto start = [&](long long k) { return cell_start ? cell_start[k] : ec_lower_bound(keys, 0, n, (unsigned long long)k); };
         int rp = order[p];                         // an ancestor of p's point, kept up to date by the hooks below
         // half stencil as five runs of the sorted order, each one grid row (cells xlo..xhi): (cy, cz) from p + 1 on (the rest of
         // p's own cell and cell cx + 1), (cy + 1, cz), and (cy - 1 .. cy + 1, cz + 1)
@@ -94,8 +85,8 @@ __global__ __launch_bounds__(256) void ec_link_kernel(const double* __restrict__
             const long long y = cy + (t == 0 ? 0 : t == 1 ? 1 : t - 3), z = cz + (t < 2 ? 0 : 1);
             if (y < 0 || y >= d1 || z >= d2) continue;
             const long long base = (z * d1 + y) * d0;
-            const int a = t == 0 ? p + 1 : start(base + xlo);
-            const int b = start(base + xhi + 1);
+            const int a = t == 0 ? p + 1 : g.start(base + xlo);
+            const int b = g.start(base + xhi + 1);
             for (int q = a; q < b; ++q) {
                 const double dx = px - cs[3 * (size_t)q], dy = py - cs[3 * (size_t)q + 1], dz = pz - cs[3 * (size_t)q + 2];
                 const double d = (dx * dx + dy * dy) + dz * dz;

@@ -21,7 +21,7 @@
 //           breadth-first search over the tight edges (dist[u] + w == dist[v]) gives every reached node its hop count, and the
 //           parent is the smallest-index tight neighbour one hop nearer - hop counts fall along every chain, so no cycle can form,
 //           zero-weight edges included.
-#include "p2w_common.h"
+#include "p2w_cells.h"
 
 namespace {            // the hand-written device-wide exclusive scan (p2w_sort.h), with internal linkage in this translation unit
 #include "p2w_sort.h"
@@ -39,22 +39,9 @@ __device__ __forceinline__ double pl_dist(const double* __restrict__ xyz, int a,
     return sqrt((dx * dx + dy * dy) + dz * dz);
 }
 
-__device__ __forceinline__ int pl_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ unsigned long long pl_load64(const unsigned long long* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // ---- kNN ----------------------------------------------------------------------------------------------------------------------
 
 __device__ __forceinline__ bool pl_less(double da, int ia, double db, int ib) { return da < db || (da == db && ia < ib); }
-
-__device__ __forceinline__ int pl_lower_bound(const unsigned long long* __restrict__ keys, int lo, int hi, unsigned long long key) {
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (keys[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 // sift the element at slot 0 down a max-heap of `cnt` entries
 __device__ __forceinline__ void pl_sift(double* hd, int* hi, int cnt) {
@@ -82,17 +69,17 @@ __global__ __launch_bounds__(PL_THREADS) void pl_knn_kernel(const double* __rest
     if (p >= n) return;
     double hd[P2W_MAX_K_WIDE];
     int hi[P2W_MAX_K_WIDE];
-    const long long d0 = gridp->dims[0], d1 = gridp->dims[1], d2 = gridp->dims[2];
+    const CellGrid g{keys, cell_start, n, gridp->dims[0], gridp->dims[1], gridp->dims[2]};
+    const long long d0 = g.d0, d1 = g.d1, d2 = g.d2;
     const double cell = (double)gridp->res;
-    const long long key = (long long)keys[p];
-    const long long cx = key % d0, cy = (key / d0) % d1, cz = key / (d0 * d1);
+    long long cx, cy, cz;
+    g.coords((long long)keys[p], cx, cy, cz);
     long long reach = cx > d0 - 1 - cx ? cx : d0 - 1 - cx;                 // the ring beyond which no cell is left
     reach = reach > cy ? reach : cy;
     reach = reach > d1 - 1 - cy ? reach : d1 - 1 - cy;
     reach = reach > cz ? reach : cz;
     reach = reach > d2 - 1 - cz ? reach : d2 - 1 - cz;
     const double px = cs[3 * (size_t)p], py = cs[3 * (size_t)p + 1], pz = cs[3 * (size_t)p + 2];
-    auto start = [&](long long c) { return cell_start ? cell_start[c] : pl_lower_bound(keys, 0, n, (unsigned long long)c); };
     int cnt = 0;
     auto run = [&](int a, int b) {
         for (int q = a; q < b; ++q) {
@@ -129,10 +116,10 @@ __global__ __launch_bounds__(PL_THREADS) void pl_knn_kernel(const double* __rest
                 const long long row = (z * d1 + y) * d0;
                 if (dz == -s || dz == s || dy == -s || dy == s) {
                     const long long xa = cx - s < 0 ? 0 : cx - s, xb = cx + s >= d0 ? d0 - 1 : cx + s;
-                    run(start(row + xa), start(row + xb + 1));
+                    run(g.start(row + xa), g.start(row + xb + 1));
                 } else {
-                    if (cx - s >= 0) run(start(row + cx - s), start(row + cx - s + 1));
-                    if (cx + s < d0) run(start(row + cx + s), start(row + cx + s + 1));
+                    if (cx - s >= 0) run(g.start(row + cx - s), g.start(row + cx - s + 1));
+                    if (cx + s < d0) run(g.start(row + cx + s), g.start(row + cx + s + 1));
                 }
             }
         }
@@ -187,7 +174,7 @@ __global__ __launch_bounds__(PL_THREADS) void pl_frontier_kernel(const double* _
         int c = 0;
         for (int j = 0, taken = 0; j < k && taken < kp1; ++j) {            // pass 1: how many edges
             const int e = row[j];
-            const int s = pl_load(step + e);
+            const int s = cells_load(step + e);
             if (s >= 0 && s < t) continue;
             ++taken;
             if (pl_dist(xyz, g, e) <= gthr) ++c;
@@ -196,7 +183,7 @@ __global__ __launch_bounds__(PL_THREADS) void pl_frontier_kernel(const double* _
         pl_append_edges(st, cap, c, edges, at);
         for (int j = 0, taken = 0; j < k && taken < kp1; ++j) {            // pass 2: the same entries (-1 and t both mean "not yet")
             const int e = row[j];
-            const int s = pl_load(step + e);
+            const int s = cells_load(step + e);
             if (s >= 0 && s < t) continue;
             ++taken;
             if (pl_dist(xyz, g, e) <= gthr) pl_put_edge(edges, cap, at++, g, e);
@@ -242,11 +229,11 @@ __global__ __launch_bounds__(PL_THREADS) void pl_gap_kernel(const double* __rest
                                                            unsigned long long* st, int* __restrict__ edges, long long cap) {
     unsigned long long* cnt_out = st + ST_CNT + (t + 1) % 3;
     for (int i = blockIdx.x * PL_THREADS + threadIdx.x; i < n; i += gridDim.x * PL_THREADS) {
-        if (pl_load(step + i) != -1) continue;
+        if (cells_load(step + i) != -1) continue;
         const int* row = nbr + (size_t)i * k;
         bool gap = false;
         for (int j = 0; j < k; ++j) {
-            const int s = pl_load(step + row[j]);
+            const int s = cells_load(step + row[j]);
             if (s >= 0 && s < t) { gap = pl_dist(xyz, i, row[j]) < thr; break; }
         }
         if (!gap) continue;
@@ -254,7 +241,7 @@ __global__ __launch_bounds__(PL_THREADS) void pl_gap_kernel(const double* __rest
         for (int side = 0; side < 2; ++side) {
             for (int j = 0, taken = 0; j < k && taken < kp1; ++j) {
                 const int e = row[j];
-                const int s = pl_load(step + e);
+                const int s = cells_load(step + e);
                 if ((s >= 0 && s < t) != (side == 0)) continue;
                 ++taken;
                 if (pl_dist(xyz, i, e) <= gthr) ++c;
@@ -265,7 +252,7 @@ __global__ __launch_bounds__(PL_THREADS) void pl_gap_kernel(const double* __rest
         for (int side = 0; side < 2; ++side) {
             for (int j = 0, taken = 0; j < k && taken < kp1; ++j) {
                 const int e = row[j];
-                const int s = pl_load(step + e);
+                const int s = cells_load(step + e);
                 if ((s >= 0 && s < t) != (side == 0)) continue;
                 ++taken;
                 if (pl_dist(xyz, i, e) <= gthr) pl_put_edge(edges, cap, at++, i, e);
@@ -346,11 +333,11 @@ __global__ __launch_bounds__(PL_THREADS) void pl_relax_kernel(const int* __restr
     unsigned long long* cnt_out = st + ST_CNT + (t + 1) % 3;
     for (int f = blockIdx.x * PL_THREADS + threadIdx.x; f < cnt_in; f += gridDim.x * PL_THREADS) {
         const int u = fin[f];
-        const double du = __longlong_as_double((long long)pl_load64(dist + u));
+        const double du = __longlong_as_double((long long)cells_load64(dist + u));
         for (int a = off[u], b = off[u + 1]; a < b; ++a) {
             const int v = adj[a];
             const unsigned long long nd = (unsigned long long)__double_as_longlong(du + w[a]);
-            if (nd < pl_load64(dist + v) && nd < atomicMin(dist + v, nd) && atomicMax(stamp + v, t + 1) < t + 1)
+            if (nd < cells_load64(dist + v) && nd < atomicMin(dist + v, nd) && atomicMax(stamp + v, t + 1) < t + 1)
                 fout[atomicAdd(cnt_out, 1ull)] = v;
         }
     }
@@ -373,7 +360,7 @@ __global__ __launch_bounds__(PL_THREADS) void pl_hop_kernel(const int* __restric
         for (int a = off[u], b = off[u + 1]; a < b; ++a) {
             const int v = adj[a];
             if ((unsigned long long)__double_as_longlong(du + w[a]) != dist[v]) continue;
-            if (pl_load(hop + v) == -1 && atomicCAS(hop + v, -1, t + 1) == -1) fout[atomicAdd(cnt_out, 1ull)] = v;
+            if (cells_load(hop + v) == -1 && atomicCAS(hop + v, -1, t + 1) == -1) fout[atomicAdd(cnt_out, 1ull)] = v;
         }
     }
 }

@@ -2,8 +2,8 @@
 
 Reference behaviour: ``pointstowood/src/io.py:11-83`` (``read_ply`` / ``write_ply``: vertex-only PLY, ascii or binary,
 output = binary little-endian with x, y, z and every other column as float64, red/green/blue as int) and
-``pointstowood/predict.py:36-52`` (``preprocess_point_cloud_data``).  numpy only; a point cloud is an ordered
-``dict`` column name -> 1-D array.
+``pointstowood/predict.py:36-52`` (``preprocess_point_cloud_data``).  numpy only (``read_ply_points`` alone hands the
+coordinates to torch); a point cloud is an ordered ``dict`` column name -> 1-D array.
 """
 from __future__ import annotations
 
@@ -55,6 +55,17 @@ def read_ply(path):
         if rec.shape[0] != n:
             raise ValueError(f"{path}: truncated PLY body ({rec.shape[0]} of {n} vertices)")
         return {name: np.ascontiguousarray(rec[name]).astype(rec[name].dtype.newbyteorder("=")) for name, _ in props}
+
+
+def read_ply_points(path):
+    """(columns, xyz [n, 3] float64 CUDA tensor) of a PLY file, for the command lines that work on a whole cloud; ``SystemExit``
+    naming the column when x, y or z is missing."""
+    import torch
+    cols = read_ply(path)
+    for c in ("x", "y", "z"):
+        if c not in cols:
+            raise SystemExit(f"{path}: no '{c}' column")
+    return cols, torch.from_numpy(np.stack([cols[c].astype(np.float64) for c in ("x", "y", "z")], axis=1)).to("cuda")
 
 
 def write_ply(path, columns, comments=()):

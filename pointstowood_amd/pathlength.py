@@ -7,8 +7,8 @@ remaining point with a processed row entry closer than ``nbrs_threshold`` and li
 first ``kpairs + 1`` unprocessed entries of its row, or, when there is none, raises the threshold by ``nbrs_threshold_step``.  Edges
 longer than ``graph_threshold`` are left out.  The path length of a point is its networkx Dijkstra distance from the base (:225).
 
-Here the same steps run in ``csrc/p2w_pathlen.hip``: the rows come from ``p2w_knn_wide_f64`` (exact float64 distances on the plot grid,
-ordered by (distance, index)), the growth from ``p2w_pathlen_grow`` and the distances from ``p2w_pathlen_sssp`` (Bellman-Ford to the
+Here the same steps run in ``csrc/p2w_pathlen.hip``: the rows come from ``p2w_knn_wide_f64`` (exact float64 distances on the plot grid
+of ``plotgrid.build``, ordered by (distance, index)), the growth from ``p2w_pathlen_grow`` and the distances from ``p2w_pathlen_sssp`` (Bellman-Ford to the
 fixed point, which is Dijkstra's result bit for bit).  Where no remaining row holds a processed point the reference raises its
 threshold for ever; here those points are reported unreached (distance NaN, step -1).
 """
@@ -20,22 +20,16 @@ import operator
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, plotgrid
 from ._lib import check, lib, ptr
+from .plotgrid import knn_slack  # noqa: F401  (a statement about the grid's construction, kept beside it)
 
 _NONFINITE = "Input contains NaN or infinity."          # what sklearn raises
-_EPS32 = 2.0 ** -23
-_TABLE_CELLS = 1 << 27
+_TABLE_CELLS = 1 << 27                                  # largest grid of the kNN whose cell table is built
 
 
 class NodeNotFound(ValueError):
     """The source of ``extract_path_info`` has no edge in the graph (networkx raises its NodeNotFound there)."""
-
-
-def knn_slack(extent: float) -> float:
-    """How far the fp32 grid can misplace a point across a cell boundary of a cloud of largest per-axis extent ``extent`` (the
-    error terms of ``cluster.safe_cell``: local coordinates and key division, each within 2^-23 E), with a factor 4 to spare."""
-    return 8.0 * _EPS32 * extent + 1e-300
 
 
 def _index(v, name):
@@ -70,51 +64,30 @@ def _check_args(n, base_id, kpairs, knn, nbrs_threshold, nbrs_threshold_step, gr
     return base_id, kpairs, knn, thr, stp, gthr
 
 
-def _as_points(xyz):
-    """(float64 CUDA tensor [n, 3], True when the caller passed numpy).  Shape and finiteness are checked on the host for numpy."""
-    if isinstance(xyz, torch.Tensor):
-        if xyz.dim() != 2 or xyz.shape[1] != 3:
-            raise ValueError(f"points must be an [n, 3] array, got shape {tuple(xyz.shape)}")
-        if not xyz.dtype.is_floating_point:
-            raise ValueError(f"points must be float32 or float64, got {xyz.dtype}")
-        _lib.require_cuda(xyz)
-        return xyz.to(torch.float64).contiguous(), False
-    a = np.asarray(xyz)
-    if a.ndim != 2 or a.shape[1] != 3:
-        raise ValueError(f"points must be an [n, 3] array, got shape {a.shape}")
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    if not np.isfinite(a).all():
+def _prepare(xyz, need_base, base_id, kpairs, knn, nbrs_threshold, nbrs_threshold_step, graph_threshold):
+    """(float64 CUDA tensor [n, 3], True when the caller passed numpy, the checked arguments).  A numpy cloud is checked on the host
+    (shape, finiteness) and uploaded only after every argument has been checked."""
+    host = not isinstance(xyz, torch.Tensor)
+    pts = np.asarray(xyz) if host else xyz
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError(f"points must be an [n, 3] array, got shape {tuple(pts.shape)}")
+    if host:
+        pts = np.ascontiguousarray(pts, dtype=np.float64)
+        if not np.isfinite(pts).all():
+            raise ValueError(_NONFINITE)
+    else:
+        if not pts.dtype.is_floating_point:
+            raise ValueError(f"points must be float32 or float64, got {pts.dtype}")
+        _lib.require_cuda(pts)
+        pts = pts.to(torch.float64).contiguous()
+    args = _check_args(pts.shape[0], base_id, kpairs, knn, nbrs_threshold, nbrs_threshold_step, graph_threshold)
+    if need_base and args[0] is None:
+        raise ValueError("base_id must be a point index")
+    if host:
+        return torch.from_numpy(pts).to("cuda"), True, args
+    if not bool(torch.isfinite(pts).all()):
         raise ValueError(_NONFINITE)
-    return a, True
-
-
-def _grid(x64: torch.Tensor, cell: float):
-    """The plot grid of ``cluster.euclidean_cluster`` (fp32 coordinates local to the minimum -> p2w_voxel_sample) at cell ``cell``:
-    (sorted float64 coordinates, order, sorted keys, grid, cell_start table or None, occupied cells)."""
-    L = lib()
-    n, dev = x64.shape[0], x64.device
-    i32 = dict(dtype=torch.int32, device=dev)
-    origin = torch.stack([x64[:, d].min() for d in range(3)])
-    rec = torch.zeros((n, 4), dtype=torch.float32, device=dev)
-    rec[:, :3] = x64 - origin
-    ptr_c = torch.tensor([0, n], **i32)
-    order, skeys = torch.empty(n, **i32), torch.empty(n, dtype=torch.int64, device=dev)
-    grid = torch.zeros(8, dtype=torch.int64, device=dev)
-    ws = torch.empty(int(L.p2w_voxel_sample_ws_bytes(n)), dtype=torch.uint8, device=dev)
-    idx, ptr_out, batch_out = torch.empty(n, **i32), torch.empty(2, **i32), torch.empty(n, **i32)
-    check(L.p2w_voxel_sample(ptr(rec), ptr(ptr_c), 1, n, float(cell), ptr(idx), ptr(ptr_out), ptr(batch_out), ptr(order),
-                             ptr(skeys), None, ptr(grid), None, None, ptr(ws), ws.numel(), _lib.stream()), "voxel_sample")
-    g = grid.cpu()
-    dims = g[4:7].tolist()
-    occupied = int(ptr_out[1].item())
-    n_cells = int(dims[0]) * int(dims[1]) * int(dims[2])
-    cell_start = None
-    if 0 < n_cells <= _TABLE_CELLS:
-        cell_start = torch.empty(n_cells + 1, **i32)
-        ws = torch.empty(int(L.p2w_cell_starts_ws_bytes(n_cells)) + 256, dtype=torch.uint8, device=dev)
-        check(L.p2w_cell_starts(ptr(skeys), n, n_cells, ptr(cell_start), ptr(ws), ws.numel(), _lib.stream()), "cell_starts")
-    cs = x64[order.long()].contiguous()
-    return cs, order, skeys, grid, cell_start, occupied
+    return pts, False, args
 
 
 def knn_rows(x64: torch.Tensor, k: int, stats: dict | None = None) -> torch.Tensor:
@@ -130,18 +103,19 @@ def knn_rows(x64: torch.Tensor, k: int, stats: dict | None = None) -> torch.Tens
     floor = extent * 2.0 ** -20
     vol = max(ext[0], floor) * max(ext[1], floor) * max(ext[2], floor)
     cell = max((vol / n * k / 2.0) ** (1.0 / 3.0), floor, 1e-9)
-    cs, order, skeys, grid, cell_start, occ = _grid(x64, cell)
+    g = plotgrid.build(x64, cell, _TABLE_CELLS)
+    occ = int(g.occupied.item())
     per = n / max(occ, 1)
     better = max(cell * min(max(math.sqrt((k / 2.0) / per), 0.125), 8.0), floor, 1e-9)
     if abs(better / cell - 1.0) > 0.25:
-        cell = better
-        del cs, order, skeys, grid, cell_start
-        cs, order, skeys, grid, cell_start, occ = _grid(x64, cell)
+        del g
+        g = plotgrid.build(x64, better, _TABLE_CELLS)
+        occ = int(g.occupied.item())
     nbr = torch.empty((n, k), dtype=torch.int32, device=x64.device)
-    check(L.p2w_knn_wide_f64(ptr(cs), ptr(order), ptr(skeys), ptr(cell_start), ptr(grid), n, k, knn_slack(extent), ptr(nbr),
-                             _lib.stream()), "knn_wide_f64")
+    check(L.p2w_knn_wide_f64(ptr(g.xyz_sorted), ptr(g.order), ptr(g.keys), ptr(g.cell_start), ptr(g.grid), n, k, knn_slack(extent),
+                             ptr(nbr), _lib.stream()), "knn_wide_f64")
     if stats is not None:
-        stats.update(knn_cell=float(np.float32(cell)), knn_occupied_cells=occ, knn_table=cell_start is not None)
+        stats.update(knn_cell=g.cell, knn_occupied_cells=occ, knn_table=g.cell_start is not None)
     return nbr
 
 
@@ -177,17 +151,6 @@ def _sssp(x64, edges, base, parents=False):
     return dist, parent, dict(sssp_rounds=int(info[0]), hop_levels=int(info[1]), sssp_launches=int(info[2]))
 
 
-def _timer(stats):
-    ev = []
-
-    def mark():
-        if stats is not None:
-            e = torch.cuda.Event(enable_timing=True)
-            e.record()
-            ev.append(e)
-    return ev, mark
-
-
 def path_length(xyz, base_id=None, kpairs=3, knn=100, nbrs_threshold=0.15, nbrs_threshold_step=0.05, graph_threshold=np.inf,
                 stats: dict | None = None):
     """(dist [n] float64, NaN where unreached; step [n] int32, -1 where never processed) of the points ``xyz`` [n, 3].
@@ -196,15 +159,12 @@ def path_length(xyz, base_id=None, kpairs=3, knn=100, nbrs_threshold=0.15, nbrs_
     The arguments are the reference's ``array_to_graph`` ones (shortest_path.py:6-8); the base has distance 0 and step 0 even when
     it has no edge.  ``stats`` (a dict, optional) receives the GPU time of the stages in ms (knn / grow / sssp, one after the other,
     each timed by events) and the counts of the growth (steps, edges, gap steps, threshold raises, launches)."""
-    pts, host = _as_points(xyz)
-    n = pts.shape[0]
-    base_id, kpairs, knn, thr, stp, gthr = _check_args(n, base_id, kpairs, knn, nbrs_threshold, nbrs_threshold_step, graph_threshold)
-    x64 = torch.from_numpy(pts).to("cuda") if host else pts
-    if not host and not bool(torch.isfinite(x64).all()):
-        raise ValueError(_NONFINITE)
+    x64, host, (base_id, kpairs, knn, thr, stp, gthr) = _prepare(xyz, False, base_id, kpairs, knn, nbrs_threshold, nbrs_threshold_step,
+                                                                 graph_threshold)
+    n = x64.shape[0]
     if base_id is None:
         base_id = int(torch.argmin(x64[:, 2]).item())
-    ev, mark = _timer(stats)
+    mark, elapsed_ms = _lib.stage_timer(stats is not None)
     mark()
     nbr = knn_rows(x64, knn, stats)
     mark()
@@ -214,8 +174,7 @@ def path_length(xyz, base_id=None, kpairs=3, knn=100, nbrs_threshold=0.15, nbrs_
     dist, _, sinfo = _sssp(x64, edges, base_id)
     mark()
     if stats is not None:
-        ev[-1].synchronize()
-        ms = [a.elapsed_time(b) for a, b in zip(ev[:-1], ev[1:])]
+        ms = elapsed_ms()
         stats.update(knn_ms=ms[0], grow_ms=ms[1], sssp_ms=ms[2], steps=int(step.max().item()), n=n, base_id=base_id, **ginfo, **sinfo)
     if host:
         return dist.cpu().numpy(), step.cpu().numpy()
@@ -264,14 +223,8 @@ class PathGraph:
 
 def array_to_graph(arr, base_id, kpairs, knn, nbrs_threshold, nbrs_threshold_step, graph_threshold=np.inf, return_step=False):
     """``array_to_graph`` of shortest_path.py:6-192 on the GPU: a ``PathGraph`` (and the step register when ``return_step``)."""
-    pts, host = _as_points(arr)
-    n = pts.shape[0]
-    base_id, kpairs, knn, thr, stp, gthr = _check_args(n, base_id, kpairs, knn, nbrs_threshold, nbrs_threshold_step, graph_threshold)
-    if base_id is None:
-        raise ValueError("base_id must be a point index")
-    x64 = torch.from_numpy(pts).to("cuda") if host else pts
-    if not host and not bool(torch.isfinite(x64).all()):
-        raise ValueError(_NONFINITE)
+    x64, _, (base_id, kpairs, knn, thr, stp, gthr) = _prepare(arr, True, base_id, kpairs, knn, nbrs_threshold, nbrs_threshold_step,
+                                                              graph_threshold)
     nbr = knn_rows(x64, knn)
     step, edges, _ = _grow(x64, nbr, base_id, kpairs, thr, stp, gthr)
     G = PathGraph(x64, edges, step)
@@ -312,17 +265,10 @@ def downsample(x64: torch.Tensor, size: float):
     fp32 coordinates local to the cloud's minimum, each occupied cell represented by its largest point index (as
     ``consecutive_cluster`` does), the representatives in ascending index order; owner[i] = the position in ``reps`` of point i's
     representative.  The reference script's ``downsample_cloud`` is not part of its tree, so this is the project's own rule."""
-    L = lib()
     n, dev = x64.shape[0], x64.device
-    i32 = dict(dtype=torch.int32, device=dev)
-    origin = torch.stack([x64[:, d].min() for d in range(3)])
-    rec = torch.zeros((n, 4), dtype=torch.float32, device=dev)
-    rec[:, :3] = x64 - origin
-    ptr_c = torch.tensor([0, n], **i32)
-    ws = torch.empty(int(L.p2w_voxel_sample_ws_bytes(n)), dtype=torch.uint8, device=dev)
-    idx, ptr_out, batch_out, inv = torch.empty(n, **i32), torch.empty(2, **i32), torch.empty(n, **i32), torch.empty(n, **i32)
-    check(L.p2w_voxel_sample(ptr(rec), ptr(ptr_c), 1, n, float(size), ptr(idx), ptr(ptr_out), ptr(batch_out), None, None, None, None,
-                             ptr(inv), None, ptr(ws), ws.numel(), _lib.stream()), "voxel_sample")
+    inv = torch.empty(n, dtype=torch.int32, device=dev)
+    # (not a plotgrid.build: the representatives and the inverse map, no sorted order or keys)
+    idx, ptr_out = plotgrid.voxel_sample(plotgrid.records(plotgrid.local(x64)[1]), size, inverse=inv)
     m = int(ptr_out[1].item())
     reps, perm = torch.sort(idx[:m].long())
     rank = torch.empty(m, dtype=torch.int64, device=dev)

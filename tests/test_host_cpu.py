@@ -601,6 +601,26 @@ def test_feature_kernels_have_no_build_switches():
         assert not hits, (src, hits)
 
 
+def test_plot_grid_is_built_in_one_place():
+    """The plot-level cell grid has one construction (plotgrid.build) and one device-side lookup (csrc/p2w_cells.h): the exactness
+    arguments of cluster.safe_cell and pathlength.knn_slack are statements about that arithmetic."""
+    import glob
+    pkg = os.path.join(ROOT, "pointstowood_amd")
+    callers = {"p2w_cell_starts(": set(), "p2w_voxel_sample(": set()}
+    for path in glob.glob(os.path.join(pkg, "*.py")):
+        text = open(path).read()
+        for call, found in callers.items():
+            if call in text:
+                found.add(os.path.basename(path))
+    assert callers["p2w_cell_starts("] == {"plotgrid.py"}
+    assert {"plotgrid.py"} <= callers["p2w_voxel_sample("] <= {"engine.py", "plotgrid.py"}      # (engine.py: its per-batch grids)
+    bounds = []
+    for src in ("p2w_cluster.hip", "p2w_pathlen.hip", "p2w_cells.h"):
+        text = open(os.path.join(pkg, "csrc", src)).read()
+        bounds += [(src, name) for name in re.findall(r"__device__[^;{()]*?\b(\w*lower_bound\w*)\s*\(", text)]
+    assert len(bounds) == 1 and bounds[0][0] == "p2w_cells.h", bounds
+
+
 def test_pick_chunk_properties():
     from pointstowood_amd.engine import pick_chunk
     rounds = lambda rows, t: -(-(-(-rows // 256) * t) // 256)
