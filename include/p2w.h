@@ -306,6 +306,26 @@ int32_t p2w_pathlen_sssp(const double* xyz, const int32_t* edges, int64_t n_edge
  * pointstowood_amd.pathlength.array_to_graph returns (shortest_path.py:241-266 add_nodes). */
 int32_t p2w_pathlen_weights(const double* xyz, const int64_t* edges, int64_t n_edges, double* w_out, p2w_stream_t stream);
 
+/* Segmented, weighted confusion matrix of a classification against truth labels: the counting behind the reference's scores -
+ * pointstowood/comparetofsct.py:85-106 and the held-out loop of pointstowood/src/trainer.py:239-242 (sklearn's precision_score,
+ * recall_score, f1_score and balanced_accuracy_score, with and without sample_weight, are all functions of this matrix).
+ * In : truth[n], pred[n] = class ids stored as floats (PLY columns, Data.y), weight[n] float64 (optional: NULL), seg_ptr[segments + 1]
+ *      int64 (DEVICE; ascending, seg_ptr[0] = 0, seg_ptr[segments] = n; NULL = one segment, segments must be 1).  truth, pred and
+ *      weight 16-byte aligned.  A point is valid when both ids are integral and in [0, classes) and its weight, where weights are
+ *      given, is finite and >= 0.
+ * Out: counts[segments][classes][classes] int64 (row = truth, column = pred) = the valid points of every cell; wsum (same shape,
+ *      float64; NULL exactly when weight is NULL) = the sum of their weights; invalid[segments] = the points that are not valid
+ *      (they enter no cell).  counts are exact; wsum has the same bits on every run (no floating-point atomics: chunks of
+ *      P2W_EVAL_CHUNK points cut at the segment boundaries are summed in a fixed order, and so are the chunks of a segment).
+ * No host synchronisation and no host read.  0 <= n <= 2^40, segments >= 1, 2 <= classes <= P2W_EVAL_MAX_CLASSES (P2W_EINVAL).
+ * ws: 16-byte aligned, p2w_confusion_ws_bytes(n, segments, classes) bytes (sized for n / P2W_EVAL_CHUNK + segments chunks). */
+#define P2W_EVAL_CHUNK 4096
+#define P2W_EVAL_MAX_CLASSES 8
+size_t p2w_confusion_ws_bytes(int64_t n, int32_t segments, int32_t classes);
+int32_t p2w_confusion(const float* truth, const float* pred, const double* weight, const int64_t* seg_ptr, int64_t n, int32_t segments,
+                      int32_t classes, int64_t* counts, double* wsum, int64_t* invalid, void* ws, size_t ws_bytes,
+                      p2w_stream_t stream);
+
 /* PointCloudClassifier.compute_labels (predicter.py:112-127) over a neighbour table nbr[n,k] (indices into pred /
  * prob, deg[i] valid entries): pwood_out = median of the neighbours' probabilities (np.median: mean of the two middle
  * values for an even count); label_out: any_wood != 1 -> 1 if any neighbour's prediction > any_wood else 0;

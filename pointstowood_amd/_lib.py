@@ -31,6 +31,7 @@ GEMM_STREAMK, GEMM_NO_STREAMK = 64, 128
 SA_ITEM_256, SA_ITEM_128, SA_PACK8 = 1, 2, 4                                                       # P2W_SA_*
 CLUSTER_LINK, CLUSTER_COMPRESS, CLUSTER_NUMBER, CLUSTER_ALL = 1, 2, 4, 7                           # P2W_CLUSTER_*
 MAX_K_WIDE = 100                                                                                   # P2W_MAX_K_WIDE
+EVAL_CHUNK, EVAL_MAX_CLASSES = 4096, 8                                                             # P2W_EVAL_*
 
 SIGNATURES = {
     "p2w_version": (_i32, []),
@@ -75,6 +76,8 @@ SIGNATURES = {
     "p2w_pathlen_sssp_ws_bytes": (_sz, [C.c_int64, C.c_int64]),
     "p2w_pathlen_sssp": (_i32, [_vp, _vp, C.c_int64, C.c_int64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "p2w_pathlen_weights": (_i32, [_vp, _vp, C.c_int64, _vp, _vp]),
+    "p2w_confusion_ws_bytes": (_sz, [C.c_int64, _i32, _i32]),
+    "p2w_confusion": (_i32, [_vp, _vp, _vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "p2w_tile_bbox": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "p2w_tile_bbox_count": (_i32, [_i32, _i32]),
     "p2w_stem": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp]),

@@ -36,6 +36,8 @@ class VoxelDataset(torch.utils.data.Dataset):
             self.keys = list(range(len(self._mem)))
         self.reflectance_index = reflectance_index
 
+    label_index = None        # column of the truth labels: ``evaluate.LabelledVoxelDataset`` sets it, and every item then carries ``y``
+
     def __len__(self):
         return len(self.keys)
 
@@ -79,10 +81,14 @@ class VoxelDataset(torch.utils.data.Dataset):
             shift = pos.mean(dim=0)
             pos = pos - shift
             sf = torch.sqrt((pos ** 2).sum(dim=1)).max()
+            y = None if self.label_index is None else pc[:, self.label_index].to(torch.float32)
             bad = torch.isnan(pos).any(dim=1) | torch.isnan(refl)
             if bool(bad.any()):
                 print(f"Encountered NaN values in sample at index {index}")
                 pos, refl = pos[~bad], refl[~bad]
+                y = None if y is None else y[~bad]
+        if y is not None:
+            return Data(pos=pos, reflectance=refl, y=y, local_shift=shift, sf=sf)
         return Data(pos=pos, reflectance=refl, local_shift=shift, sf=sf)
 
 
