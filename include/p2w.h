@@ -472,7 +472,14 @@ int32_t p2w_gemm_h2_rowdot(int32_t prec, const void* A_h, int32_t ldh_a, const v
  * ldp >= round_up(C1, K granularity) floats: rows 0..n_src-1 = x_src * W1x^T + b1 with ZERO pad columns; row n_src is the row
  * empty neighbour slots read (the kernel's loads are unconditional): it must EXIST, the call fills it with zeros itself (the only
  * write through P).
- * ws: 16-byte aligned scratch of >= p2w_sa_conv_h_ws_bytes(M, flags) bytes for the per-edge metadata (P2W_EWORKSPACE otherwise);
+ * Outputs (either pointer may be NULL, not both): out[M, ldo] fp32 - the call writes columns 0..C2-1 of rows 0..M-1 and nothing
+ * else; out_h = an H tensor of row pitch ldh (ldh >= C2, a multiple of 8; of 32 for F16X3) - the call writes the C2 output
+ * columns and ZEROS in the columns from C2 up to min(ldh, round_up(C2, W)), W = the width of a work item's column tile: 256
+ * (C2 > 128, or P2W_SA_ITEM_256) or 128 (C2 <= 128, or P2W_SA_ITEM_128).  So the zero pad up to round_up(C2, K granularity)
+ * is always written when ldh covers it, a wider row may be zeroed up to the end of the last column tile, and no column from
+ * round_up(C2, 256) on is ever touched.  Rows >= M are never written.
+ * ws: 16-byte aligned scratch of >= p2w_sa_conv_h_ws_bytes(M, flags) bytes for the per-edge metadata (P2W_EWORKSPACE otherwise; what it
+ * holds on entry does not matter: the call's pre-pass writes every word its kernels read);
  * kw <= 32 (one 32-row MFMA tile per target); round_up(C1, K granularity) <= 512, C2 <= 1024 (LDS tables), M < 2^25 and
  * (n_src + 1) * ldp < 2^33 (32-bit offsets) - P2W_EUNSUPPORTED otherwise. */
 size_t p2w_sa_conv_h_ws_bytes(int32_t M, int32_t flags);
