@@ -542,6 +542,32 @@ int32_t p2w_rowdot(const float* x, int32_t ldx, int32_t F, const float* w, float
 /* FPModule 4 (model.py:236): the coarse level has ONE point per voxel: nbr[q] = batch[q], deg = 1. */
 int32_t p2w_fill_batch_nbr(const int32_t* batch, int32_t m, int32_t* nbr, int32_t* deg, p2w_stream_t stream);
 
+/* ---- backward passes of the operator route (pointstowood_amd/ops.py) ---- */
+/* No floating-point atomics: the same bits on every run.  The fused p2w_sa_conv* and the GEMMs have no backward. */
+
+/* p2w_segment_max plus its winners: out[B, F] (dense) holds the bits p2w_segment_max gives; arg[b, c] (int32, dense [B, F]) = the
+ * lowest row of ptr[b] .. ptr[b+1] whose value equals out[b, c], -1 for an empty segment (out = 0) and for a column of NaNs only.
+ * 16-byte accesses when F and ldx are multiples of 4 and x, out, arg are 16-byte aligned, 4-byte accesses otherwise. */
+int32_t p2w_segment_max_arg(const float* x, int32_t ldx, int32_t F, const int32_t* ptr, int32_t B, float* out, int32_t* arg,
+                            p2w_stream_t stream);
+/* Its gradient, a gather: grad_x[r, c] = (arg[b(r), c] == r) ? grad_out[b(r), c] : 0 for r < n, c < F, b(r) the segment of row r
+ * (ptr[0] = 0; rows from ptr[B] on get 0).  Every element is written exactly once: the caller does not clear grad_x.  The whole
+ * gradient of a tied maximum goes to the lowest row. */
+int32_t p2w_segment_max_bwd(const float* grad_out, int32_t ldg, const int32_t* arg, const int32_t* ptr, int32_t B, int32_t F,
+                            float* grad_x, int32_t ldx, int32_t n, p2w_stream_t stream);
+/* Gradient of knn_interpolate (p2w_interp_concat without skip) with respect to the coarse features:
+ *   grad_x[j, 0:F] = sum over the slots (q, s), s < deg[q], nbr[q, s] == j, of a(q, s) * grad_out[q, 0:F],
+ * a(q, s) = w / sum_s w, w = 1 / max(d2, 1e-16) as in the forward (the sum in slot order), for every j < n_coarse: a row nobody
+ * references gets zeros.  The slots are transposed with p2w_sort_pairs_u64 (key = j, value = q kw + s: stable, so a row's slots
+ * stay ascending) and p2w_cell_starts; a row's run is summed in fp32 in ascending slot order by the row lanes of one block and,
+ * where the mean run is long (one coarse point per voxel), by several blocks, and combined in a tree fixed by the sizes.
+ * 1 <= kw <= P2W_MAX_K_WIDE (else P2W_EINVAL); F, ldg, ldx multiples of 4 (else P2W_EINVAL); grad_out, grad_x, xyzr_*, ws 16-byte
+ * aligned (else P2W_EALIGN); ws: p2w_interp_bwd_ws_bytes(m, kw, n_coarse) bytes (0 = bad sizes; too small: P2W_EWORKSPACE). */
+size_t p2w_interp_bwd_ws_bytes(int32_t m, int32_t kw, int32_t n_coarse);
+int32_t p2w_interp_bwd(const float* grad_out, int32_t ldg, int32_t F, const float* xyzr_c, const float* xyzr_f, const int32_t* nbr,
+                       const int32_t* deg, int32_t kw, int32_t m, int32_t n_coarse, float* grad_x, int32_t ldx, void* ws,
+                       size_t ws_bytes, p2w_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

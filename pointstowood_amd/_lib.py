@@ -106,6 +106,10 @@ SIGNATURES = {
     "p2w_segment_max": (_i32, [_vp, _i32, _i32, _vp, _i32, _vp, _vp]),
     "p2w_rowdot": (_i32, [_vp, _i32, _i32, _vp, _f32, _i32, _vp, _vp]),
     "p2w_fill_batch_nbr": (_i32, [_vp, _i32, _vp, _vp, _vp]),
+    "p2w_segment_max_arg": (_i32, [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "p2w_segment_max_bwd": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp]),
+    "p2w_interp_bwd_ws_bytes": (_sz, [_i32, _i32, _i32]),
+    "p2w_interp_bwd": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -16,6 +16,11 @@ Every function requires CUDA (MI355X) tensors and libp2w_gfx950.so; there is no 
 Index results are int64 like the reference's; the kernels work in int32 internally.
 ``Net.forward`` does not go through these wrappers (it keeps padded neighbour tables and
 fuses the message/aggregate step); they exist for operator-level drop-in use and tests.
+
+Gradients: ``global_max_pool``, ``scatter_max`` (and with it ``MessagePassing.propagate``) and ``knn_interpolate`` are
+differentiable with respect to their features (HIP backward kernels, ``csrc/p2w_grad.hip``, the same bits on every run);
+positions, batch vectors and indices get none.  A tied maximum sends its whole gradient to the lowest row.  The fused
+``PointNetConv`` and ``Net.forward`` stay inference-only.
 """
 from __future__ import annotations
 
@@ -126,41 +131,122 @@ def knn(x, y, k, batch_x=None, batch_y=None, cosine=False, num_workers=1):
     return _edges(*_search("knn", x, y, None, batch_x, batch_y, int(k)))
 
 
+def _wants_grad(x):
+    return torch.is_grad_enabled() and x.requires_grad
+
+
+def _pad4(x):
+    """fp32, contiguous, rows padded to a multiple of 4 floats (the interpolation kernels' 16-byte accesses)."""
+    F0 = x.shape[1]
+    F = (F0 + 3) // 4 * 4
+    xc = x.to(torch.float32)
+    if F != F0:
+        xc = torch.nn.functional.pad(xc, (0, F - F0))
+    return xc.contiguous(), F
+
+
+class _SegmentMax(torch.autograd.Function):
+    """Segment max that keeps its winners (``p2w_segment_max_arg``) for the gather of the backward
+    (``p2w_segment_max_bwd``).  The arg table is saved for backward only."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, x, csr, nb):
+        xc = x.to(torch.float32).contiguous()
+        n, F = xc.shape
+        out = torch.empty((nb, F), dtype=torch.float32, device=x.device)
+        arg = torch.empty((nb, F), dtype=torch.int32, device=x.device)
+        check(lib().p2w_segment_max_arg(ptr(xc), F, F, ptr(csr), nb, ptr(out), ptr(arg), stream()), "segment_max_arg")
+        ctx.save_for_backward(arg, csr)
+        ctx.shape, ctx.dtype = (n, F), x.dtype
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_out):
+        arg, csr = ctx.saved_tensors
+        n, F = ctx.shape
+        g = grad_out.to(torch.float32).contiguous()
+        grad_x = torch.empty((n, F), dtype=torch.float32, device=g.device)
+        check(lib().p2w_segment_max_bwd(ptr(g), F, ptr(arg), ptr(csr), arg.shape[0], F, ptr(grad_x), F, n, stream()),
+              "segment_max_bwd")
+        return grad_x.to(ctx.dtype), None, None
+
+
 def global_max_pool(x, batch, size=None):
+    """Differentiable with respect to ``x`` (``batch`` gets no gradient).  Tie rule: the whole gradient of a column goes to
+    the lowest row that holds the segment's maximum.  (PyTorch's ``scatter_reduce(amax)`` splits it evenly among the tied
+    rows; the two rules give the same parameter gradients wherever the tied values are equal outputs of the same layer -
+    the ReLU zeros after ``local_nn``.)  Without a gradient to track the launches and the bits are those of
+    ``p2w_segment_max`` alone."""
     _lib.require_cuda(x, batch)
     nb = _num_batches(batch) if size is None else int(size)
+    csr = _csr(batch, nb)
+    if _wants_grad(x):
+        return _SegmentMax.apply(x, csr, nb)
     x = x.to(torch.float32).contiguous()
     out = torch.empty((nb, x.shape[1]), dtype=torch.float32, device=x.device)
-    csr = _csr(batch, nb)
     check(lib().p2w_segment_max(ptr(x), x.shape[1], x.shape[1], ptr(csr), nb, ptr(out), stream()), "global_max_pool")
     return out
 
 
 def scatter_max(src, index, dim=0, out=None, dim_size=None):
-    """Sorted-index segment max (the reference's index is the query-major edge target, pointnet.py:122)."""
+    """Sorted-index segment max (the reference's index is the query-major edge target, pointnet.py:122).  Differentiable
+    with respect to ``src`` with ``global_max_pool``'s tie rule (lowest row wins); the second result stays ``None``."""
     assert dim == 0
     res = global_max_pool(src.reshape(src.shape[0], -1), index, size=dim_size)
     return res.reshape((res.shape[0],) + tuple(src.shape[1:])), None
 
 
+def _interp_forward(x, rc, rf, nbr, deg, k):
+    m, F0 = rf.shape[0], x.shape[1]
+    xc, F = _pad4(x)
+    out = torch.empty((m, F), dtype=torch.float32, device=x.device)
+    check(lib().p2w_interp_concat(ptr(xc), F, ptr(rc), ptr(rf), ptr(nbr), ptr(deg), int(k), None, 0, m,
+                                  ptr(out), F, stream()), "knn_interpolate")
+    return out if F == F0 else out[:, :F0].contiguous()
+
+
+class _KnnInterpolate(torch.autograd.Function):
+    """``p2w_interp_concat`` forward, ``p2w_interp_bwd`` backward: gradient with respect to the coarse features only."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, x, rc, rf, nbr, deg, k):
+        ctx.save_for_backward(rc, rf, nbr, deg)
+        ctx.k, ctx.shape, ctx.dtype = int(k), tuple(x.shape), x.dtype
+        return _interp_forward(x, rc, rf, nbr, deg, k)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_out):
+        rc, rf, nbr, deg = ctx.saved_tensors
+        (n, F0), m = ctx.shape, rf.shape[0]
+        g, F = _pad4(grad_out)
+        grad_x = torch.empty((n, F), dtype=torch.float32, device=g.device)
+        need = int(lib().p2w_interp_bwd_ws_bytes(m, ctx.k, n))
+        if need == 0:
+            raise RuntimeError("p2w_interp_bwd_ws_bytes failed")
+        ws = torch.empty(need, dtype=torch.uint8, device=g.device)
+        check(lib().p2w_interp_bwd(ptr(g), F, F, ptr(rc), ptr(rf), ptr(nbr), ptr(deg), ctx.k, m, n, ptr(grad_x), F,
+                                   ptr(ws), ws.numel(), stream()), "knn_interpolate backward")
+        if F != F0:
+            grad_x = grad_x[:, :F0].contiguous()
+        return grad_x.to(ctx.dtype), None, None, None, None, None
+
+
 def knn_interpolate(x, pos_x, pos_y, batch_x=None, batch_y=None, k=3, num_workers=1):
     """PyG's signature and default (k = 3); any 1 <= k <= 100 and any feature width (rows are padded to a multiple of 4
-    floats for the kernel's 16-byte accesses)."""
+    floats for the kernel's 16-byte accesses).  Differentiable with respect to ``x``; positions and batch vectors get no
+    gradient."""
     _lib.require_cuda(x, pos_x, pos_y)
     if not 1 <= k <= 100:
         raise RuntimeError("knn_interpolate: k must be in 1..100")
     nbr, deg = _search("knn", pos_x, pos_y, None, batch_x, batch_y, int(k))
-    m, F0 = pos_y.shape[0], x.shape[1]
-    F = (F0 + 3) // 4 * 4
-    xc = x.to(torch.float32)
-    if F != F0:
-        xc = torch.nn.functional.pad(xc, (0, F - F0))
-    xc = xc.contiguous()
-    out = torch.empty((m, F), dtype=torch.float32, device=x.device)
     rc, rf = _xyzr(pos_x), _xyzr(pos_y)   # keep both alive until the launch is enqueued
-    check(lib().p2w_interp_concat(ptr(xc), F, ptr(rc), ptr(rf), ptr(nbr), ptr(deg), int(k), None, 0, m,
-                                  ptr(out), F, stream()), "knn_interpolate")
-    return out if F == F0 else out[:, :F0].contiguous()
+    if _wants_grad(x):
+        return _KnnInterpolate.apply(x, rc, rf, nbr, deg, int(k))
+    return _interp_forward(x, rc, rf, nbr, deg, k)
 
 
 # --------------------------------------------------------------------------- the 8th operator
@@ -221,7 +307,9 @@ def _local_nn_weights(local_nn):
     except (TypeError, IndexError) as e:
         raise NotImplementedError("the fused PointNetConv supports local_nn = MLP([F_in + 4, C1, C2]) as the reference builds it") from e
     if bn.training:
-        raise RuntimeError("pointstowood_amd.ops.PointNetConv is inference-only: call .eval()")
+        raise RuntimeError("pointstowood_amd.ops.PointNetConv is inference-only: call .eval().  The route that trains is "
+                           "the unfused one: the reference's own PointNetConv subclass over ops.MessagePassing "
+                           "(its scatter_max has a backward)")
     s = (bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps))
     t = bn.bias.double() - bn.running_mean.double() * s
     return lin1.weight, lin1.bias, lin2.weight, lin2.bias, s.float(), t.float()
