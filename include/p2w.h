@@ -326,6 +326,29 @@ int32_t p2w_confusion(const float* truth, const float* pred, const double* weigh
                       int32_t classes, int64_t* counts, double* wsum, int64_t* invalid, void* ws, size_t ws_bytes,
                       p2w_stream_t stream);
 
+/* Poly-1 focal loss of the reference's training step, forward and backward in one pass: Poly1FocalLoss.forward
+ * (pointstowood/src/loss.py:28-73, the criterion of pointstowood/src/trainer.py:174-202) evaluated per element in fp32, statement by
+ * statement - logits clamped to [-10, 10], optional label smoothing, sigmoid clamped to [eps, 1 - eps], BCE-with-logits times weight
+ * clamped at 100, pt clamped, (1 - pt)^gamma clamped at 2, optional alpha_t, the poly term epsilon * (1 - pt)^(gamma + 1) clamped at
+ * 100, the sum clamped to [0, 100], NaN replaced by 0.
+ * In : logits[n], labels[n] float32; weight: NULL (weight_n = 0), one element (weight_n = 1) or n elements (weight_n = n), float32,
+ *      DEVICE memory; the reference's scalars as doubles, rounded to fp32 where the reference's fp32 tensors meet them.  alpha and
+ *      label_smoothing are "not set" (the reference's None) when they are NaN; every other scalar must be finite, gamma >= 0 and
+ *      0 < eps < 0.5 (P2W_EINVAL).  logits, labels, an n-element weight, loss and dloss 16-byte aligned.
+ * Out, each optional (NULL = not wanted, neither computed nor written): loss[n] float32 = the per-element loss; dloss[n] float32 =
+ *      the derivative of element i's loss with respect to logit i under PyTorch's autograd conventions (a clamp passes the gradient
+ *      inside its closed range and gives 0 outside; the BCE term's derivative is (sigmoid(z) - y) * weight of the clamped logit z; a
+ *      zero exponent contributes nothing) - 0 for a logit beyond +-10 or NaN, never NaN for finite labels and weights; sum[1] float64 =
+ *      the sum of the per-element losses, the same bits on every run (no atomics, no memset: one float64 partial per chunk of
+ *      P2W_LOSS_CHUNK elements, lanes, waves and chunks added in an order fixed by n alone).  n = 0 writes sum = 0 and reads nothing.
+ * Two launches (one without sum), no host synchronisation and no host read.  0 <= n <= 2^40 (P2W_EINVAL).
+ * ws: needed only with sum; 16-byte aligned, p2w_poly1_focal_ws_bytes(n) bytes (0 for an n out of range). */
+#define P2W_LOSS_CHUNK 4096
+size_t p2w_poly1_focal_ws_bytes(int64_t n);
+int32_t p2w_poly1_focal(const float* logits, const float* labels, const float* weight, int64_t weight_n, int64_t n, double epsilon,
+                        double gamma, double alpha, double label_smoothing, double eps, float* loss, float* dloss, double* sum,
+                        void* ws, size_t ws_bytes, p2w_stream_t stream);
+
 /* PointCloudClassifier.compute_labels (predicter.py:112-127) over a neighbour table nbr[n,k] (indices into pred /
  * prob, deg[i] valid entries): pwood_out = median of the neighbours' probabilities (np.median: mean of the two middle
  * values for an even count); label_out: any_wood != 1 -> 1 if any neighbour's prediction > any_wood else 0;

@@ -8,3 +8,4 @@ __version__ = "0.1.0"
 
 from .model import Net, checkpoint_layout  # noqa: E402,F401
 from .data import Batch, Data, DataLoader  # noqa: E402,F401
+from .loss import Poly1FocalLoss  # noqa: E402,F401

@@ -32,6 +32,7 @@ SA_ITEM_256, SA_ITEM_128, SA_PACK8 = 1, 2, 4                                    
 CLUSTER_LINK, CLUSTER_COMPRESS, CLUSTER_NUMBER, CLUSTER_ALL = 1, 2, 4, 7                           # P2W_CLUSTER_*
 MAX_K_WIDE = 100                                                                                   # P2W_MAX_K_WIDE
 EVAL_CHUNK, EVAL_MAX_CLASSES = 4096, 8                                                             # P2W_EVAL_*
+LOSS_CHUNK = 4096                                                                                  # P2W_LOSS_CHUNK
 
 SIGNATURES = {
     "p2w_version": (_i32, []),
@@ -78,6 +79,9 @@ SIGNATURES = {
     "p2w_pathlen_weights": (_i32, [_vp, _vp, C.c_int64, _vp, _vp]),
     "p2w_confusion_ws_bytes": (_sz, [C.c_int64, _i32, _i32]),
     "p2w_confusion": (_i32, [_vp, _vp, _vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "p2w_poly1_focal_ws_bytes": (_sz, [C.c_int64]),
+    "p2w_poly1_focal": (_i32, [_vp, _vp, _vp, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp,
+                               _vp, _sz, _vp]),
     "p2w_tile_bbox": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "p2w_tile_bbox_count": (_i32, [_i32, _i32]),
     "p2w_stem": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp]),
@@ -180,6 +184,12 @@ def require_cuda(*tensors):
         if t is not None and not t.is_cuda:
             raise RuntimeError("pointstowood_amd operators need tensors on an MI355X (cuda) device; "
                                "there is no CPU fallback")
+
+
+def aligned16(t):
+    """Kernels that read 16 bytes at a time need their arrays on a 16-byte boundary: a view that starts inside its storage
+    (``x[1:]``) is copied."""
+    return t.clone() if t.data_ptr() % 16 else t
 
 
 def packed_dims(n: int, k: int, prec: int | None = None):

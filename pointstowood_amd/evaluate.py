@@ -22,15 +22,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check, lib, ptr as _p
+from ._lib import aligned16 as _aligned, check, lib, ptr as _p
 from .predicter import VoxelDataset, prefetch_batches
 
 METRICS = ("precision", "recall", "f1", "balanced_accuracy", "accuracy")
-
-
-def _aligned(t: torch.Tensor) -> torch.Tensor:
-    """The kernel reads with 16-byte loads: a view that starts inside its storage (``x[1:]``) is copied."""
-    return t.clone() if t.data_ptr() % 16 else t
 
 
 def confusion(truth, pred, weight=None, ptr=None, classes: int = 2, strict: bool = True, out=None):
