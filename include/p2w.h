@@ -365,7 +365,8 @@ int32_t p2w_tile_bbox_count(int32_t B, int32_t n_bound);
 
 /* ---- features ---------------------------------------------------------- */
 
-/* stem_mlp: out[n,C] = relu(W[C,3] * xyz + b) - model.py:208,228. */
+/* stem_mlp: out[n,C] = relu(W[C,3] * xyz + b) - model.py:208,228.  C a multiple of 4; xyzr and out 16-byte aligned (P2W_EALIGN:
+ * the rows are written 16 bytes at a time). */
 int32_t p2w_stem(const float* xyzr, int32_t n, const float* w, const float* b, int32_t C, float* out,
                  p2w_stream_t stream);
 
@@ -523,7 +524,9 @@ int32_t p2w_sa_conv_h_rows(int32_t prec, const float* P, int32_t ldp, int32_t n_
 /* The small kernels writing H (and fp32 where given): stem (model.py:208,228), knn_interpolate + cat (:149-151),
  * cat(x, pos) (:135).  For the stem and the interpolation `ldh` is the row pitch as in p2w_gemm_h2: they write their columns
  * (C, resp. Fc + Fs) plus the zero pad to the next K-slab boundary and leave the rest of a wider row alone (p2w_interp_concat_h2
- * with skip = NULL, Fs = 0 writes only the interpolated part of a row whose skip columns another producer has written). */
+ * with skip = NULL, Fs = 0 writes only the interpolated part of a row whose skip columns another producer has written).
+ * All three write 16 bytes at a time: `out` (fp32, where given) and `out_h` must be 16-byte aligned (P2W_EALIGN), as the inputs
+ * they read 16 bytes at a time (xyzr, xc, skip, x). */
 /* range (p2w_stem_h2, p2w_stem_h2_indexed, p2w_sa_conv_h_rows; NULL = off): the range watch of p2w_epilogue.range - a device
  * block of P2W_RANGE_WORDS words (the caller zeroes them). */
 int32_t p2w_stem_h2(int32_t prec, const float* xyzr, int32_t n, const float* w, const float* b, int32_t C, float* out,
@@ -550,7 +553,8 @@ int32_t p2w_interp_concat(const float* xc, int32_t Fc, const float* xyzr_c, cons
                           const int32_t* deg, int32_t kw, const float* skip, int32_t Fs, int32_t m, float* out,
                           int32_t ldo, p2w_stream_t stream);
 
-/* [x | xyz] concat feeding GlobalSAModule.NN - model.py:135. */
+/* [x | xyz] concat feeding GlobalSAModule.NN - model.py:135.  out[q] = [x[q, 0:F] | x, y, z | 0 ...] up to ldo (the record's .w
+ * does not enter); F and ldo multiples of 4, ldo >= F + 4; x, xyzr and out 16-byte aligned (P2W_EALIGN). */
 int32_t p2w_concat_xyz(const float* x, int32_t F, const float* xyzr, int32_t m, float* out, int32_t ldo,
                        p2w_stream_t stream);
 

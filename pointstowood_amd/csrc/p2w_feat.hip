@@ -611,6 +611,8 @@ static int32_t stem_launch(int32_t prec, const float* xyzr, int32_t n, const flo
     if (n == 0) return P2W_OK;
     P2W_CHECK_PTR(xyzr); P2W_CHECK_PTR(w); P2W_CHECK_PTR(b); P2W_CHECK_ALIGN16(xyzr);
     if (!out && !out_h2) return P2W_ENULL;
+    if (out) P2W_CHECK_ALIGN16(out);          // (float4 stores through both)
+    if (out_h2) P2W_CHECK_ALIGN16(out_h2);
     if (n < 0 || C <= 0 || (C & 3) || (out_h2 && (ldh < C || (ldh & 7)))) return P2W_EINVAL;
     const int ka = prec == P2W_PREC_F16X3 ? 32 : 64;
     const int hcols = out_h2 ? (ldh < (C + ka - 1) / ka * ka ? ldh : (C + ka - 1) / ka * ka) : 0;   // C channels + zero pad to the K-slab boundary
@@ -817,6 +819,8 @@ static int32_t concat_launch(int32_t prec, const float* x, int32_t F, const floa
     P2W_CHECK_PTR(x); P2W_CHECK_PTR(xyzr);
     if (!out && !out_h2) return P2W_ENULL;
     P2W_CHECK_ALIGN16(x); P2W_CHECK_ALIGN16(xyzr);
+    if (out) P2W_CHECK_ALIGN16(out);
+    if (out_h2) P2W_CHECK_ALIGN16(out_h2);
     if (m < 0 || F <= 0 || (F & 3)) return P2W_EINVAL;
     if (out && ((ldo & 3) || ldo < F + 4)) return P2W_EINVAL;
     if (out_h2 && ((ldh & 7) || ldh < F + 4)) return P2W_EINVAL;

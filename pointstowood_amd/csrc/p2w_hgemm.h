@@ -174,6 +174,10 @@ __device__ __forceinline__ void range_commit(unsigned* __restrict__ dst, bool ov
         if (seen) p[1] = 1u;
     }
 }
+// The watch's running maximum must KEEP a NaN (it is reported as OVER: !(m <= P2W_RANGE_HI)); fmaxf returns the other operand,
+// so a NaN beside a number - or behind the running maximum's initial 0 - went unreported.  IEEE-754 maximum: v_maximum3_f32 on
+// gfx950, the same instruction count as v_max3_f32.
+__device__ __forceinline__ float nan_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }
 // ... from a per-lane maximum of |value|
 __device__ __forceinline__ void range_commit_max(unsigned* __restrict__ dst, float m, int lane) {
     range_commit(dst, __ballot(!(m <= P2W_RANGE_HI)) != 0ull, __ballot(m > P2W_RANGE_LO) != 0ull, lane);
@@ -360,7 +364,7 @@ __device__ __forceinline__ void gemm_epilogue_16(const f32x4 (&acc)[RT16][CT16],
             for (int jq = 0; jq < JQ; ++jq) {
                 const float va = value(acc[it][2 * jq][reg], bias[jq][0], s0[jq][0], t0[jq][0], s1[jq][0], t1[jq][0], rcur[jq][0]);
                 const float vb = value(acc[it][2 * jq + 1][reg], bias[jq][1], s0[jq][1], t0[jq][1], s1[jq][1], t1[jq][1], rcur[jq][1]);
-                m4 = fmaxf(m4, fmaxf(fabsf(va), fabsf(vb)));     // (one v_max3 per column pair)
+                m4 = nan_max(nan_max(m4, fabsf(va)), fabsf(vb));     // (one v_maximum3 per column pair)
                 if (DOT) dsum = fmaf(vb, dw[jq][1], fmaf(va, dw[jq][0], dsum));
                 if (OF) *reinterpret_cast<fpair*>(fp + 32 * jq) = fpair{va, vb};
                 if (OH) {
@@ -411,7 +415,7 @@ __device__ __forceinline__ void gemm_epilogue_16(const f32x4 (&acc)[RT16][CT16],
                         if (OF && cv) o.f32[(size_t)row * o.ldo + c + e] = v[e];
                     }
                     {
-                        const float m2 = fmaxf(fabsf(v[0]), fabsf(v[1]));
+                        const float m2 = nan_max(fabsf(v[0]), fabsf(v[1]));
                         r_over |= __ballot(!(m2 <= P2W_RANGE_HI));
                         r_seen |= __ballot(m2 > P2W_RANGE_LO);
                     }
@@ -1021,7 +1025,7 @@ __device__ __forceinline__ void sa_epilogue_regs(const f32x16 (&acc)[RT][2], flo
                 }
                 float vmax = fmaf(fmaxf(fmaf(sgn * ext, wscale, e.bias[j]), 0.f), e.s[j], e.t[j]);
                 if (d == 0 || !cv) vmax = 0.f;   // rows without neighbours; pad columns of an H row stay zero
-                amax = fmaxf(amax, fabsf(vmax));
+                amax = nan_max(amax, fabsf(vmax));   // (keeps a NaN: range_commit_max reports it as OVER)
                 if (cv && h == 0 && out) out[(size_t)tgt * ldo + col] = vmax;
                 if (out_h2) {  // lanes (2p, 2p+1) hold adjacent columns: the even lane stores both as one word per plane
                     const float nb = __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(vmax), 0xB1, 0xf, 0xf, false));

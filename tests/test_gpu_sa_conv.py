@@ -269,6 +269,11 @@ def test_range_report(prec):
     w = words()
     _run(case, prec, range_words=w, bn_t=hot)
     assert report(w) == (True, True)
+    nan_t = case["bn_t"].clone()
+    nan_t[5] = float("nan")                                               # a NaN output is OVER too (include/p2w.h)
+    w = words()
+    _run(case, prec, range_words=w, bn_t=nan_t)
+    assert report(w)[0]
 
 
 # ---- j. the fp32 path ----------------------------------------------------------------------------------------------------

@@ -177,8 +177,9 @@ def test_binding_signatures_match_the_header_prototypes():
 
 def test_header_compiles_as_c_and_the_library_links(tmp_path):
     """include/p2w.h is a C header (no C++ leaks) and libp2w_gfx950.so is an ordinary shared library: a C program built with gcc
-    calls the version / error-string / packed-dimension helpers and gets the documented status from an argument error - no Python,
-    no torch, no GPU.  The library exports the p2w_* ABI and nothing else."""
+    calls the version / error-string / packed-dimension helpers and gets the documented status from every argument error of the
+    small feature and geometry entry points (fake addresses: a status that comes back before the launch needs no GPU) - no Python,
+    no torch.  The library exports the p2w_* ABI and nothing else."""
     import shutil
     import subprocess
     _lib.lib()
@@ -200,6 +201,93 @@ int main(void) {
     if (np != 256 || kp != 96) return 3;
     if (p2w_gemm_h2(7, (const void*)16, 32, (const void*)16, 1.0f, 4, 4, 4, &e, (float*)16, 4, 0, 0, 0, 0) != P2W_EINVAL) return 4;
     if (p2w_gemm_h2_sk_ws_bytes() == 0) return 5;
+    /* argument errors of the small feature / geometry entry points: every status below comes back before a launch.
+     * A = some 16-byte aligned address, U = one that is not; neither is ever dereferenced. */
+#define A(T) ((T*)16)
+#define U(T) ((T*)20)
+#define F_ const float
+#define I_ const int32_t
+#define CK(call, want) do { if ((call) != (want)) { printf("line %d: %d\\n", __LINE__, (int)(call)); return 10; } } while (0)
+    CK(p2w_pack_xyzr(0, 3, 0, 0, 1, 0, 0, 0, 0), P2W_OK);
+    CK(p2w_pack_xyzr(0, 3, A(F_), A(I_), 1, 5, A(float), A(int32_t), 0), P2W_ENULL);
+    CK(p2w_pack_xyzr(A(F_), 3, 0, A(I_), 1, 5, A(float), 0, 0), P2W_ENULL);
+    CK(p2w_pack_xyzr(A(F_), 3, 0, A(I_), 1, 5, U(float), A(int32_t), 0), P2W_EALIGN);
+    CK(p2w_pack_xyzr(A(F_), 2, 0, A(I_), 1, 5, A(float), A(int32_t), 0), P2W_EINVAL);
+    CK(p2w_pack_xyzr(A(F_), 3, 0, A(I_), 0, 5, A(float), A(int32_t), 0), P2W_EINVAL);
+    CK(p2w_pack_xyzr(A(F_), 3, 0, A(I_), 1, -5, A(float), A(int32_t), 0), P2W_EINVAL);
+    CK(p2w_level_gather(0, 0, 0, 0, 1, 0, 0, 0, 0), P2W_OK);
+    CK(p2w_level_gather(A(F_), A(I_), A(I_), A(I_), 1, 5, 0, A(float), 0), P2W_ENULL);
+    CK(p2w_level_gather(A(F_), 0, A(I_), A(I_), 1, 5, A(F_), A(float), 0), P2W_ENULL);
+    CK(p2w_level_gather(A(F_), A(I_), A(I_), A(I_), 1, 5, A(F_), U(float), 0), P2W_EALIGN);
+    CK(p2w_level_gather(U(F_), A(I_), A(I_), A(I_), 1, 5, A(F_), A(float), 0), P2W_EALIGN);
+    CK(p2w_level_gather(A(F_), A(I_), A(I_), A(I_), 0, 5, A(F_), A(float), 0), P2W_EINVAL);
+    CK(p2w_level_gather(A(F_), A(I_), A(I_), A(I_), 1, -5, A(F_), A(float), 0), P2W_EINVAL);
+    CK(p2w_fill_batch_nbr(0, 0, 0, 0, 0), P2W_OK);
+    CK(p2w_fill_batch_nbr(0, 5, A(int32_t), A(int32_t), 0), P2W_ENULL);
+    CK(p2w_fill_batch_nbr(A(I_), 5, A(int32_t), 0, 0), P2W_ENULL);
+    CK(p2w_fill_batch_nbr(A(I_), -5, A(int32_t), A(int32_t), 0), P2W_EINVAL);
+    CK(p2w_stem(A(F_), 5, A(F_), A(F_), 8, 0, 0), P2W_ENULL);
+    CK(p2w_stem(A(F_), 5, 0, A(F_), 8, A(float), 0), P2W_ENULL);
+    CK(p2w_stem(U(F_), 5, A(F_), A(F_), 8, A(float), 0), P2W_EALIGN);
+    CK(p2w_stem(A(F_), 5, A(F_), A(F_), 8, U(float), 0), P2W_EALIGN);
+    CK(p2w_stem(A(F_), 5, A(F_), A(F_), 6, A(float), 0), P2W_EINVAL);
+    CK(p2w_stem(A(F_), -5, A(F_), A(F_), 8, A(float), 0), P2W_EINVAL);
+    CK(p2w_stem(A(F_), 0, A(F_), A(F_), 8, A(float), 0), P2W_OK);
+    CK(p2w_stem_h2(3, A(F_), 5, A(F_), A(F_), 8, A(float), A(void), 32, 0, 0), P2W_EINVAL);
+    CK(p2w_stem_h2(0, A(F_), 5, A(F_), A(F_), 8, 0, 0, 32, 0, 0), P2W_ENULL);
+    CK(p2w_stem_h2(0, A(F_), 5, A(F_), A(F_), 8, U(float), A(void), 32, 0, 0), P2W_EALIGN);
+    CK(p2w_stem_h2(1, A(F_), 5, A(F_), A(F_), 8, 0, U(void), 64, 0, 0), P2W_EALIGN);
+    CK(p2w_stem_h2(0, A(F_), 5, A(F_), A(F_), 40, 0, A(void), 32, 0, 0), P2W_EINVAL);
+    CK(p2w_stem_h2(0, A(F_), 5, A(F_), A(F_), 8, 0, A(void), 12, 0, 0), P2W_EINVAL);
+    CK(p2w_stem_h2_indexed(-1, A(F_), 5, A(F_), A(F_), 8, A(float), A(void), 32, 0, 0), P2W_EINVAL);
+    CK(p2w_stem_h2_indexed(2, A(F_), 5, A(F_), 0, 8, A(float), A(void), 64, 0, 0), P2W_ENULL);
+    CK(p2w_stem_h2_indexed(2, A(F_), 5, A(F_), A(F_), 8, 0, 0, 64, 0, 0), P2W_ENULL);
+    CK(p2w_stem_h2_indexed(2, A(F_), 5, A(F_), A(F_), 8, U(float), 0, 0, 0, 0), P2W_EALIGN);
+    CK(p2w_stem_h2_indexed(2, A(F_), 5, A(F_), A(F_), 8, A(float), U(void), 64, 0, 0), P2W_EALIGN);
+    CK(p2w_stem_h2_indexed(2, A(F_), 5, A(F_), A(F_), 6, A(float), A(void), 64, 0, 0), P2W_EINVAL);
+    CK(p2w_interp_concat(A(F_), 8, A(F_), A(F_), A(I_), A(I_), 2, 0, 0, 5, 0, 8, 0), P2W_ENULL);
+    CK(p2w_interp_concat(A(F_), 8, A(F_), A(F_), A(I_), A(I_), 2, 0, 4, 5, A(float), 12, 0), P2W_ENULL);
+    CK(p2w_interp_concat(A(F_), 8, A(F_), A(F_), A(I_), A(I_), 2, 0, 0, 5, U(float), 8, 0), P2W_EALIGN);
+    CK(p2w_interp_concat(A(F_), 8, A(F_), A(F_), A(I_), A(I_), 2, U(F_), 4, 5, A(float), 12, 0), P2W_EALIGN);
+    CK(p2w_interp_concat(A(F_), 6, A(F_), A(F_), A(I_), A(I_), 2, 0, 0, 5, A(float), 8, 0), P2W_EINVAL);
+    CK(p2w_interp_concat(A(F_), 8, A(F_), A(F_), A(I_), A(I_), 0, 0, 0, 5, A(float), 8, 0), P2W_EINVAL);
+    CK(p2w_interp_concat(A(F_), 8, A(F_), A(F_), A(I_), A(I_), 2, A(F_), 4, 5, A(float), 8, 0), P2W_EINVAL);
+    CK(p2w_interp_concat_h2(0, A(F_), 8, A(F_), A(F_), A(I_), A(I_), 2, 0, 0, 5, 0, 32, 0), P2W_ENULL);
+    CK(p2w_interp_concat_h2(3, A(F_), 8, A(F_), A(F_), A(I_), A(I_), 2, 0, 0, 5, A(void), 32, 0), P2W_EINVAL);
+    CK(p2w_interp_concat_h2(0, A(F_), 8, A(F_), A(F_), A(I_), A(I_), 2, 0, 0, 5, U(void), 32, 0), P2W_EALIGN);
+    CK(p2w_interp_concat_h2(0, A(F_), 8, A(F_), A(F_), A(I_), A(I_), 2, 0, 0, 5, A(void), 12, 0), P2W_EINVAL);
+    CK(p2w_interp_concat_h2(0, A(F_), 40, A(F_), A(F_), A(I_), A(I_), 2, 0, 0, 5, A(void), 32, 0), P2W_EINVAL);
+    CK(p2w_interp_weights(0, 0, 0, 0, 2, 0, 0, 0), P2W_OK);
+    CK(p2w_interp_weights(A(F_), A(F_), A(I_), A(I_), 2, 5, 0, 0), P2W_ENULL);
+    CK(p2w_interp_weights(A(F_), A(F_), A(I_), A(I_), 2, 5, U(void), 0), P2W_EALIGN);
+    CK(p2w_interp_weights(A(F_), A(F_), A(I_), A(I_), 0, 5, A(void), 0), P2W_EINVAL);
+    CK(p2w_interp_weights(A(F_), A(F_), A(I_), A(I_), 2, -5, A(void), 0), P2W_EINVAL);
+    CK(p2w_interp_weights(A(F_), A(F_), A(I_), A(I_), 3, 5, A(void), 0), P2W_EUNSUPPORTED);
+    CK(p2w_concat_xyz(A(F_), 8, A(F_), 5, 0, 12, 0), P2W_ENULL);
+    CK(p2w_concat_xyz(0, 8, A(F_), 5, A(float), 12, 0), P2W_ENULL);
+    CK(p2w_concat_xyz(U(F_), 8, A(F_), 5, A(float), 12, 0), P2W_EALIGN);
+    CK(p2w_concat_xyz(A(F_), 8, A(F_), 5, U(float), 12, 0), P2W_EALIGN);
+    CK(p2w_concat_xyz(A(F_), 6, A(F_), 5, A(float), 12, 0), P2W_EINVAL);
+    CK(p2w_concat_xyz(A(F_), 8, A(F_), 5, A(float), 8, 0), P2W_EINVAL);
+    CK(p2w_concat_xyz(A(F_), 8, A(F_), 0, A(float), 12, 0), P2W_OK);
+    CK(p2w_concat_xyz_h2(0, A(F_), 8, A(F_), 5, 0, 32, 0), P2W_ENULL);
+    CK(p2w_concat_xyz_h2(5, A(F_), 8, A(F_), 5, A(void), 32, 0), P2W_EINVAL);
+    CK(p2w_concat_xyz_h2(0, A(F_), 8, A(F_), 5, U(void), 32, 0), P2W_EALIGN);
+    CK(p2w_concat_xyz_h2(1, A(F_), 8, A(F_), 5, A(void), 8, 0), P2W_EINVAL);
+    CK(p2w_concat_xyz_h2(1, A(F_), 8, A(F_), 5, A(void), 20, 0), P2W_EINVAL);
+    CK(p2w_segment_max(0, 8, 8, A(I_), 2, A(float), 0), P2W_ENULL);
+    CK(p2w_segment_max(A(F_), 8, 8, A(I_), 2, 0, 0), P2W_ENULL);
+    CK(p2w_segment_max(A(F_), 8, 8, A(I_), 0, A(float), 0), P2W_EINVAL);
+    CK(p2w_segment_max(A(F_), 7, 8, A(I_), 2, A(float), 0), P2W_EINVAL);
+    CK(p2w_segment_max(A(F_), 8, 0, A(I_), 2, A(float), 0), P2W_EINVAL);
+    CK(p2w_rowdot(0, 8, 8, 0, 0.f, 0, 0, 0), P2W_OK);
+    CK(p2w_rowdot(A(F_), 8, 8, 0, 0.f, 5, A(float), 0), P2W_ENULL);
+    CK(p2w_rowdot(A(F_), 8, 8, A(F_), 0.f, 5, 0, 0), P2W_ENULL);
+    CK(p2w_rowdot(U(F_), 8, 8, A(F_), 0.f, 5, A(float), 0), P2W_EALIGN);
+    CK(p2w_rowdot(A(F_), 8, 8, U(F_), 0.f, 5, A(float), 0), P2W_EALIGN);
+    CK(p2w_rowdot(A(F_), 8, 6, A(F_), 0.f, 5, A(float), 0), P2W_EINVAL);
+    CK(p2w_rowdot(A(F_), 4, 8, A(F_), 0.f, 5, A(float), 0), P2W_EINVAL);
+    CK(p2w_rowdot(A(F_), 8, 8, A(F_), 0.f, -5, A(float), 0), P2W_EINVAL);
     printf("abi ok %d %zu\\n", (int)p2w_version(), sizeof(p2w_epilogue));
     return 0;
 }
