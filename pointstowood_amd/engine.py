@@ -194,16 +194,110 @@ class Geometry:
     fp_nbr: dict = field(default_factory=dict)   # fine level f -> (nbr [n,2], deg) into level f+1
     counts_dev: torch.Tensor | None = None
     counts_host: torch.Tensor | None = None
-    done: object = None
+    done: object = None                          # event: the last search has finished
+    args: tuple = ()                             # (pos, reflectance, ptr0, sf) this geometry was enqueued for (a redo repeats them)
+    stream: object = None                        # the stream the sampling chain was enqueued on
+    search_stream: object = None                 # the stream of the searches where that is another one (the lone forward)
+    table_levels: list = field(default_factory=list)   # levels sampled through the cell table (their status word is meaningful)
+    table_probes: list = field(default_factory=list)   # ... of these, the ones handed out BELOW the remembered growth factor
+    order: torch.Tensor | None = None            # level 0: input index of every position of the sampler's cell order
+    sorted0: torch.Tensor | None = None          # level 0's records in that order
+    rows0_sorted: bool = False                   # the feature phase keeps level 0's rows in that order (fp1_cell_order)
+    order64: torch.Tensor | None = None          # ... then: `order` as int64
+    inv0: torch.Tensor | None = None             # ... and its inverse
+    pstride: int = 0                             # counts_host: level l's CSR starts at (l - 1) * pstride, the status words at 3 * pstride
+    sizes_ready: object = None                   # event: the sampling chain and the copy to counts_host have finished
+    ev_nbr: dict = field(default_factory=dict)   # search_stream only: level -> event of its SA search
+    ev_fp: dict = field(default_factory=dict)    # ... fine level -> event of its interpolation search
+    aux: list = field(default_factory=list)      # device tensors the searches and the feature phase read besides the ones above
+    launch_searches: object = None               # callable(count=None, after=None) while searches are still to be enqueued
+    early: dict | None = None                    # what _features_early enqueued ahead of the host's wait for the sizes
+    watch: object = None                         # the feature phase's range report (Engine._range_end)
+    lone: bool = False                           # a lone forward (EngineOptions.single_res_streams chunk chains), not the pipeline
 
     def tensors(self):
+        """Every device tensor a feature phase reads (Net.stream records them on the feature stream)."""
         out = [self.sf, self.counts_dev]
         for lv in self.levels:
             out += [t for t in (lv.xyzr, lv.ptr, lv.batch, lv.idx, lv.nbr, lv.deg) if t is not None]
         for nbr, deg in self.fp_nbr.values():
             out += [nbr, deg]
-        out += list(getattr(self, "aux", []))
+        out += self.aux + list(self.args)
         return [t for t in out if t is not None]
+
+
+@dataclass(frozen=True)
+class HLayout:
+    """Shape of the H tensors (16-bit planes of GEMM operands) of one precision: rows are zero-padded to whole K slabs of the GEMM
+    so that they can be DMA-staged; f16x3 keeps a hi and a lo fp16 plane side by side per slab."""
+    slab: int             # columns per K slab: 32 (f16x3) / 64
+    planes: int           # 2 (f16x3) / 1
+    dtype: torch.dtype
+
+    def pitch(self, f):   # padded row pitch (in columns) of f feature columns
+        return (f + self.slab - 1) // self.slab * self.slab
+
+    def new(self, rows, f, dev):
+        return torch.empty((rows, self.planes * self.pitch(f)), dtype=self.dtype, device=dev)
+
+    def col(self, t, c):  # view of the H tensor t from column c on (c a multiple of the slab width)
+        return t[:, self.planes * c:]
+
+
+class TableProvision:
+    """When a level's grid sub-sampling takes the direct cell table, and how large a one (host arithmetic only).  Provision: B voxels
+    x the cells of a 2.3 m cube at the level's resolution (+ margin), times the level's growth factor (x 8 after every overflow,
+    i.e. twice the extent per axis).  The kernels clear, scan and compact only the part of the table the batch's real grid uses,
+    so a generous capacity costs (almost) nothing - what costs is the GRID: it grows with the number of voxels, the sort with
+    the number of points.  Many small voxels (B in the hundreds, a few hundred points each) mean tens of millions of cells for
+    half a million points, so the table is only taken while the grid of B nominal voxels has at most ``table_cells_per_point``
+    cells per point.  ``options`` carries that and ``sampler`` (the engine: read at every call)."""
+    CELLS_MAX = 1 << 26          # 64 M entries x 20 B = 1.3 GB of workspace at most
+    SCALE_MAX = 64               # growth factor cap of a level's table after overflows
+    REST = 64                    # a level that overflows even at that scale (voxels > 9 m, non-finite coordinates) takes the sort for this many
+                                 # batches before the table is tried again: such a workload pays the discarded geometry pass once per 64 batches
+
+    def __init__(self, options):
+        self.options = options
+        self.scale = [1, 1, 1]        # per level: grows by 8 (up to SCALE_MAX) after an overflow
+        self.rest = [0, 0, 0]         # per level: batches the table sits out after overflowing at its largest scale
+        self.probe_rest = [0, 0, 0]   # per level: oversized batches that take the sort before the next probe
+
+    def cells(self, level, B, N):
+        """(table capacity in entries for `level`'s sampler, 0 = use the sort; is it a probe: smaller than the remembered factor asks for)."""
+        if self.options.sampler != "table":
+            return 0, False
+        if self.rest[level] > 0:
+            self.rest[level] -= 1
+            return 0, False
+        per_voxel = (int(2.3 / SA_RES[level]) + 3) ** 3
+        if B * per_voxel > self.options.table_cells_per_point * max(N, 1):
+            return 0, False
+        # the growth factor this level has needed so far is kept (round 4: a 67-voxel batch of 4 m plot voxels shrank it back to 1,
+        # overflowed, and paid a discarded geometry pass + the sort on every forward)
+        cells = B * per_voxel * self.scale[level]
+        if cells <= self.CELLS_MAX:
+            return cells, False
+        # That extent does not fit for THIS many voxels.  The factor is one number per level, but batches differ: after a batch of 4 m
+        # plot voxels (factor 8) every later batch of many NOMINAL voxels would take the sort for the life of the engine (ADVICE r4).
+        # So such a batch PROBES the largest smaller factor that fits (overflowed() says what a failed probe costs).
+        if self.probe_rest[level] > 0:
+            self.probe_rest[level] -= 1
+            return 0, False
+        s = self.scale[level]
+        while s > 1 and B * per_voxel * s > self.CELLS_MAX:
+            s //= 8
+        cells = B * per_voxel * s
+        return (cells, True) if cells <= self.CELLS_MAX else (0, False)
+
+    def overflowed(self, level, was_probe):
+        """The table `cells` handed out for `level` did not hold the batch's grid (one discarded geometry pass): more room next time."""
+        if was_probe:     # not answered by growing the factor: no probing for REST oversized batches (they take the sort)
+            self.probe_rest[level] = self.REST
+            return
+        if self.scale[level] >= self.SCALE_MAX:
+            self.rest[level] = self.REST     # no more room to give: the sort serves the next batches
+        self.scale[level] = min(self.scale[level] * 8, self.SCALE_MAX)
 
 
 def pick_chunk(m: int, budget: int, col_tiles: int, n_cu: int = 256, full_rounds: bool = False) -> int:
@@ -324,10 +418,15 @@ class Engine:
         self.options = options if options is not None else EngineOptions(**kw)
         for name in EngineOptions.names():      # the switches live on the engine (tools flip them between runs)
             setattr(self, name, getattr(self.options, name))
-        self._table_scale = [1, 1, 1]   # per level: grows by 8 (up to TABLE_SCALE_MAX) after an overflow
-        self._table_rest = [0, 0, 0]    # per level: batches the table sits out after overflowing at its largest scale
-        self._table_probe = [False, False, False]   # per level: the table just handed out was smaller than the remembered factor (a probe)
-        self._table_probe_rest = [0, 0, 0]          # per level: oversized batches that take the sort before the next probe
+        self.h = {"f16x3": HLayout(32, 2, torch.float16), "fp16": HLayout(64, 1, torch.float16), "bf16": HLayout(64, 1, torch.bfloat16)}.get(precision)
+        self._table = TableProvision(self)   # (next line: its per-level lists under the names tests and tools read)
+        self._table_scale, self._table_rest, self._table_probe_rest = self._table.scale, self._table.rest, self._table.probe_rest
+        self._side_streams = {}     # feature stream -> its second chunk-chain stream
+        self._search_streams = {}   # caller stream -> the lone forward's search stream
+        self._sk_ws = {}            # stream -> its stream-K workspace
+        self._zeros_c = {}          # (B, device) -> the pooled level's all-zero positions
+        self._s_geo = self._s_feat = None   # the pipeline's streams (made by the first forward_stream)
+        self._seen_warned = False
         self._ws_t = None
         self._range = None        # range watch of the feature phase being enqueued: (layer names, device floats)
         self.fallback = None      # callable(geo, keep) -> logits on an arithmetic without the range limit (Net: the fp32 engine)
@@ -343,19 +442,45 @@ class Engine:
         self._ws = None
 
     # -- small helpers ------------------------------------------------------------------------
-    def _chains(self):
+    def _chains(self, geo):
         """Chunk chains in flight inside one feature phase: EngineOptions.res_streams in the stream pipeline (which keeps two whole
         phases in flight), EngineOptions.single_res_streams in a lone forward (nothing else fills its round tails)."""
-        return max(1, int(self.single_res_streams if getattr(self, "_lone", False) else self.res_streams))
+        return max(1, int(self.single_res_streams if geo.lone else self.res_streams))
 
-    def _side_stream(self, cur):
-        """The second chunk-chain stream of the feature phase running on `cur` (one per feature stream: phases in flight on
-        different streams must not meet on a shared side stream)."""
-        pool = self.__dict__.setdefault("_side_streams", {})
-        key = cur.cuda_stream
+    @staticmethod
+    def _companion(pool, priority):
+        """The side stream (made at first use) that `pool` keeps for the current stream."""
+        key = _lib.stream()
         if key not in pool:
-            pool[key] = torch.cuda.Stream(priority=int(self.res_priority))
+            pool[key] = torch.cuda.Stream(priority=int(priority))
         return pool[key]
+
+    def _chunk_chains(self, geo, M, width, col_tiles, full_rounds, lane_bufs, body):
+        """``body(r0, m, bufs)`` over the M rows of a level in row chunks: independent chains of GEMMs whose intermediates (``width``
+        columns) are written and re-read while they still sit in the 256 MiB Infinity Cache instead of round-tripping HBM.  The
+        chunks alternate between the current stream and (with more than one chain, _chains) its side stream, so that the tiles of
+        one chain fill the CUs the other leaves idle at its wave tails (a 1122-row tail chunk at level 3 otherwise runs four GEMMs
+        at 16 % chip fill); every lane owns the ``lane_bufs(rows)``.  Everything behind the join is ordered behind both chains."""
+        chunk = (self.res_chunk_rows if self.res_chunk_rows > 0 else M) * 512 // width    # ~same bytes per chunk at every level
+        chunk = max(256, min(M, pick_chunk(M, chunk, col_tiles, full_rounds=full_rounds and self.chunk_full_rounds and not self.gemm_stream_k)
+                             if self.chunk_pick else chunk // 256 * 256))
+        cur = torch.cuda.current_stream()
+        lanes = [cur]
+        if min(self._chains(geo), -(-M // chunk)) > 1:
+            # one side stream per feature stream: phases in flight on different streams must not meet on a shared one
+            lanes.append(self._companion(self._side_streams, self.res_priority))
+        bufs = [lane_bufs(min(M, chunk)) for _ in lanes]
+        if len(lanes) > 1:
+            ready = torch.cuda.Event()
+            ready.record(cur)
+            lanes[1].wait_event(ready)
+        for ci, r0 in enumerate(range(0, M, chunk)):
+            with torch.cuda.stream(lanes[ci % len(lanes)]):
+                body(r0, min(chunk, M - r0), bufs[ci % len(lanes)])
+        if len(lanes) > 1:
+            done = torch.cuda.Event()
+            done.record(lanes[1])
+            cur.wait_event(done)
 
     def _call(self, name, fn, *args):
         ev = self.events
@@ -390,54 +515,15 @@ class Engine:
             self.events.append(tuple(self._open))
             self._open = None
 
+    @staticmethod
+    def _epilogue(lin: Linear, residual=None, ldr=0, *watch_interp):
+        """The p2w_epilogue of `lin` (+ its residual operand; + range-watch word, interpolation records and rows of the H GEMMs)."""
+        return Epilogue(ptr(lin.bias), ptr(lin.sc0), ptr(lin.sh0), ptr(lin.sc1), ptr(lin.sh1), ptr(residual), ldr,
+                        lin.relu0, lin.relu1, lin.relu2, lin.relu_final, *watch_interp)
+
     def _gemm(self, name, A, lda, M, lin: Linear, out, ldo, residual=None, ldr=0):
-        ep = Epilogue(ptr(lin.bias), ptr(lin.sc0), ptr(lin.sh0), ptr(lin.sc1), ptr(lin.sh1), ptr(residual), ldr,
-                      lin.relu0, lin.relu1, lin.relu2, lin.relu_final)
+        ep = self._epilogue(lin, residual, ldr)
         self._call(name, lib().p2w_gemm, ptr(A), lda, ptr(lin.w), M, lin.N, lin.K, C.byref(ep), ptr(out), ldo)
-
-    TABLE_CELLS_MAX = 1 << 26          # 64 M entries x 20 B = 1.3 GB of workspace at most
-    TABLE_SCALE_MAX = 64               # growth factor cap of a level's table after overflows
-    TABLE_REST = 64                    # a level that overflows even at that scale (voxels > 9 m, non-finite coordinates) takes the
-                                       # sort for this many batches before the table is tried again: a workload of such batches
-                                       # pays the discarded geometry pass once per 64 batches instead of on every one
-
-    def _table_cells(self, level, B, N):
-        """Table capacity (entries) for the sampler of `level`, 0 = use the sort.  Provision: B voxels x the cells of a 2.3 m cube
-        at that resolution (+ margin), times the level's growth factor (x 8 after every overflow, i.e. twice the extent per
-        axis; a batch for which that does not fit TABLE_CELLS_MAX takes the sort).  The kernels clear, scan and compact only the part of the table the batch's real
-        grid uses, so a generous capacity costs (almost) nothing - what costs is the GRID: it grows with the number of voxels,
-        the sort with the number of points.  Many small voxels (B in the hundreds, a few hundred points each) mean tens of
-        millions of cells for half a million points, so the table is only taken while the grid of B nominal voxels has at
-        most ``table_cells_per_point`` cells per point.  Decided per batch; only the growth factor is remembered."""
-        if self.sampler != "table":
-            return 0
-        if self._table_rest[level] > 0:
-            self._table_rest[level] -= 1
-            return 0
-        per_voxel = (int(2.3 / SA_RES[level]) + 3) ** 3
-        if B * per_voxel > self.table_cells_per_point * max(N, 1):
-            return 0
-        # the growth factor this level has needed so far (x 8 per overflow).  If a table of that extent does not fit for THIS batch's
-        # voxel count, take the sort: a smaller table is the one that already overflowed (round 4: a 67-voxel batch of 4 m plot
-        # voxels shrank the factor back to 1, overflowed, and paid a discarded geometry pass + the sort on every forward)
-        cells = B * per_voxel * self._table_scale[level]
-        if cells <= self.TABLE_CELLS_MAX:
-            return cells
-        # The remembered extent does not fit for THIS many voxels.  The factor is one number per level, but batches differ: after a
-        # batch of 4 m plot voxels (factor 8) every later batch of many NOMINAL voxels would take the sort for the life of the engine
-        # (ADVICE r4).  So such a batch PROBES the largest smaller factor that fits - a probe that overflows costs one discarded
-        # geometry pass, is not answered by growing the factor, and silences probing for TABLE_REST batches (they take the sort).
-        if self._table_probe_rest[level] > 0:
-            self._table_probe_rest[level] -= 1
-            return 0
-        s = self._table_scale[level]
-        while s > 1 and B * per_voxel * s > self.TABLE_CELLS_MAX:
-            s //= 8
-        cells = B * per_voxel * s
-        if cells > self.TABLE_CELLS_MAX:
-            return 0
-        self._table_probe[level] = True
-        return cells
 
     def _table_workspace(self, n, cells, device):
         need = int(lib().p2w_voxel_sample_table_ws_bytes(n, cells))
@@ -464,41 +550,41 @@ class Engine:
         SEARCHES.  ``search_stream`` None: all on the current stream.  Otherwise (the single-call forward) the searches go to
         that stream behind the sampling chain and every search records an event (``geo.ev_nbr[l]``, ``geo.ev_fp[f]``) that the
         feature phase waits for where it first reads the result: the searches of level l + 1 then run BESIDE the features of
-        level l.  All buffers are allocated on the current stream either way.  ``defer_searches``: the caller enqueues them
-        itself (``geo.launch_searches()``) - the lone forward puts its size-independent feature kernels in front of them."""
+        level l.  Every buffer - the searches' outputs included - is allocated here, on the current stream, before ``sizes_ready``
+        is recorded; only the searches' LAUNCHES go to ``search_stream``.  That stream waits for ``sizes_ready`` before it writes
+        them, and ``forward()`` ends with the caller's stream waiting for ``geo.done``, so the caller's allocator pool never
+        recycles them under the side stream.  ``defer_searches``: the caller enqueues the searches itself
+        (``geo.launch_searches()``) - the lone forward puts its size-independent feature kernels in front of them."""
         L = lib()
         dev = pos.device
         N, B, k = pos.shape[0], sf.numel(), self.k
         i32 = dict(dtype=torch.int32, device=dev)
         f32 = dict(dtype=torch.float32, device=dev)
         i64 = dict(dtype=torch.int64, device=dev)
-        geo = Geometry(B=B, N=N, k=k, sf=sf)
-        geo.args = (pos, reflectance, ptr0, sf)
-        geo.stream = torch.cuda.current_stream()
-        geo.search_stream = search_stream
+        geo = Geometry(B=B, N=N, k=k, sf=sf, args=(pos, reflectance, ptr0, sf), stream=torch.cuda.current_stream(),
+                       search_stream=search_stream)
         # the three levels' CSR arrays and the table sampler's status words live in ONE buffer, so that the level sizes
         # (ptr_l[B]) and the status reach the host in one copy without a gather kernel in front of it
         pstride = (B + 1 + 3) // 4 * 4
         meta = torch.empty(3 * pstride + 4, **i32)
         status = meta[3 * pstride:]       # per level: 1 = the table sampler's grid did not fit (results undefined)
-        geo.table_levels = []
-        geo.table_probes = []      # levels whose table was handed out BELOW the remembered growth factor (see _table_cells)
         xyzr0, batch0 = torch.empty((N, 4), **f32), torch.empty(N, **i32)
         self._call("pack_xyzr", L.p2w_pack_xyzr, ptr(pos), pos.stride(0), ptr(reflectance), ptr(ptr0), B, N,
                    ptr(xyzr0), ptr(batch0))
         geo.levels.append(Level(xyzr=xyzr0, ptr=ptr0, batch=batch0, n=N))
         ws = self._workspace(N, dev)
         nbox = int(L.p2w_tile_bbox_count(B, N))
-        bbox = {}   # level -> tile bounding boxes of that level's records (kNN pruning; results unchanged)
+        grid_search = self.search != "brute"   # brute: whole-voxel streaming kernels (A/B, tests)
+        # brute: tile bounding boxes of level 0's cell-sorted records and of levels 1..3 (kNN pruning; results unchanged)
+        box0, bbox = (None, {}) if grid_search else (torch.empty((nbox, 6), **f32), {l: torch.empty((nbox, 6), **f32) for l in (1, 2, 3)})
+        boxed = set()
 
         def boxes(level):
-            if level not in bbox:
-                t = torch.empty((nbox, 6), **f32)
+            if level not in boxed:
                 lv_ = geo.levels[level]
-                self._call("tile_bbox", L.p2w_tile_bbox, ptr(lv_.xyzr), ptr(lv_.ptr), B, N, ptr(t))
-                bbox[level] = t
+                self._call("tile_bbox", L.p2w_tile_bbox, ptr(lv_.xyzr), ptr(lv_.ptr), B, N, ptr(bbox[level]))
+                boxed.add(level)
             return bbox[level]
-        grid_search = self.search != "brute"   # brute: whole-voxel streaming kernels (A/B, tests)
         sorted0 = skeys0 = None   # level 0 in cell order (the level-1 sampler's sort), each record carrying its own index
         ckeys, grids, ranks = {}, {}, {}     # level -> cell key of every record (ascending) / p2w_grid of the sampling call
         cstart, cstart0 = {}, None           # level -> cell -> position table of its records (table sampler only)
@@ -514,9 +600,8 @@ class Engine:
             # rank of every source point's cell among the sampled level (= index of its representative): seeds the
             # interpolation searches (level 0 takes part in its sorted order, so it needs the rank per sorted position)
             ranks[l] = torch.empty(N, **i32) if (grid_search and self.fp_hints) else None
-            self._table_probe[l] = False
-            cells = 0 if force_sort else self._table_cells(l, B, N)
-            if self._table_probe[l]:
+            cells, probe = (0, False) if force_sort else self._table.cells(l, B, N)
+            if probe:
                 geo.table_probes.append(l)
             if cells:
                 ws_t = self._table_workspace(N, cells, dev)
@@ -549,19 +634,18 @@ class Engine:
             self._call("level_gather", L.p2w_level_gather, ptr(src.xyzr), ptr(lv.idx), ptr(lv.batch), ptr(lv.ptr), B, N,
                        ptr(sf), ptr(lv.xyzr))
             geo.levels.append(lv)
+        # the interpolation searches' results and hints (both of a point's two nearest coarse points are within its cell: the
+        # representative's / a storage neighbour's representative's distance)
+        for f in (2, 1, 0):
+            geo.fp_nbr[f] = (torch.empty((N, 2), **i32), torch.empty(N, **i32))
+        hints = {f: torch.empty(N, **f32) for f in (2, 1, 0) if ranks[f] is not None}
         # the level sizes (and the table sampler's status words) start their way to the host here, ahead of the searches
-        geo.counts_dev = meta
+        geo.counts_dev, geo.pstride = meta, pstride
         geo.counts_host = torch.empty(meta.numel(), dtype=torch.int32, pin_memory=True)
         geo.counts_host.copy_(meta, non_blocking=True)
-        geo.pstride = pstride
         geo.sizes_ready = torch.cuda.Event()
         geo.sizes_ready.record()
         # ---- searches (as a closure: the lone forward enqueues its size-independent feature kernels between the two chains)
-        geo.ev_nbr, geo.ev_fp = {}, {}
-
-        def searching():
-            return torch.cuda.stream(search_stream) if search_stream is not None else contextlib.nullcontext()
-
         def mark(table, key):
             if search_stream is not None:
                 table[key] = torch.cuda.Event()
@@ -576,11 +660,9 @@ class Engine:
                                ptr(cstart0), ptr(src.xyzr), ptr(lv.idx), ptr(lv.ptr), B, N, res * 2, k, ptr(lv.nbr), ptr(lv.deg),
                                SEARCH_X_INDEX_IN_W | (SEARCH_BOX if self.search_box & 1 else 0))
                 else:
-                    box0 = torch.empty((nbox, 6), **f32)
                     self._call("tile_bbox", L.p2w_tile_bbox, ptr(sorted0), ptr(src.ptr), B, N, ptr(box0))
                     self._call("ball_query", L.p2w_ball_query, ptr(sorted0), ptr(src.ptr), ptr(src.xyzr), ptr(lv.idx),
                                ptr(lv.ptr), B, N, res * 2, k, ptr(lv.nbr), ptr(lv.deg), ptr(box0), SEARCH_X_INDEX_IN_W)
-                    geo.aux.append(box0)
             elif grid_search:   # model.py:120
                 self._call("knn", L.p2w_knn_grid_indexed, ptr(src.xyzr), ptr(ckeys[l]), ptr(src.ptr), ptr(grids[l]), ptr(cstart.get(l)),
                            ptr(src.xyzr),
@@ -594,24 +676,21 @@ class Engine:
         def fp_search(f):
             # k=2 searches of knn_interpolate (model.py:149): fine level f queries coarse level f+1
             fine, coarse = geo.levels[f], geo.levels[f + 1]
-            nbr, deg = torch.empty((N, 2), **i32), torch.empty(N, **i32)
+            nbr, deg = geo.fp_nbr[f]
             # level 0 queries run over the cell-sorted copy; their result rows go to the points' own rows (row in .w) - or stay in
             # cell order when the feature phase keeps level 0 in that order (fp1_cell_order)
-            q, fl = (sorted0, 0 if getattr(geo, "rows0_sorted", False) else SEARCH_Q_ROW_IN_W) if f == 0 else (fine.xyzr, 0)
+            q, fl = (sorted0, 0 if geo.rows0_sorted else SEARCH_Q_ROW_IN_W) if f == 0 else (fine.xyzr, 0)
             if grid_search:
-                hint = None
-                if ranks.get(f) is not None:   # both of a point's two nearest coarse points are within its cell
-                    hint = torch.empty(N, **f32)   # representative's / a storage neighbour's representative's distance
+                hint = hints.get(f)
+                if hint is not None:
                     self._call("knn_hint", L.p2w_knn_hint2, ptr(q), ptr(ranks[f]), ptr(fine.ptr), B, N, ptr(coarse.xyzr),
                                ptr(hint))
-                    geo.aux.append(hint)
                 self._call("knn2", L.p2w_knn_grid_indexed, ptr(coarse.xyzr), ptr(ckeys[f + 1]), ptr(coarse.ptr), ptr(grids[f + 1]),
                            ptr(cstart.get(f + 1)), ptr(q), None, ptr(fine.ptr), B, N, 2, ptr(nbr), ptr(deg), ptr(hint),
                            fl | (SEARCH_BOX if self.search_box & 4 else 0))
             else:
                 self._call("knn2", L.p2w_knn, ptr(coarse.xyzr), ptr(coarse.ptr), ptr(q), None, ptr(fine.ptr), B, N, 2,
                            ptr(nbr), ptr(deg), ptr(boxes(f + 1)), fl)
-            geo.fp_nbr[f] = (nbr, deg)
             mark(geo.ev_fp, f)
         jobs = [lambda l=l: sa_search(l) for l in range(3)] + [lambda f=f: fp_search(f) for f in (2, 1, 0)]
 
@@ -626,27 +705,24 @@ class Engine:
                 search_stream.wait_event(geo.sizes_ready)
             if after is not None and search_stream is not None:
                 search_stream.wait_event(after)
-            with searching():
+            with torch.cuda.stream(search_stream) if search_stream is not None else contextlib.nullcontext():
                 for job in todo:
                     job()
                 if not jobs:
-                    geo.done = torch.cuda.Event()
+                    geo.launch_searches, geo.done = None, torch.cuda.Event()
                     geo.done.record()
-            if not jobs:
-                geo.launch_searches = None
-                geo.aux += list(bbox.values())
-        aux0 += list(ckeys.values()) + list(grids.values()) + [t for t in ranks.values() if t is not None]
-        aux0 += [t for t in list(cstart.values()) + [cstart0] if t is not None]
-        if getattr(geo, "rows0_sorted", False):
-            aux0 += [geo.inv0, geo.order64]
-        geo.aux = aux0
+        aux0 += [box0, cstart0, geo.inv0, geo.order64]
+        for d in (bbox, hints, ckeys, grids, ranks, cstart):
+            aux0 += d.values()
+        geo.aux = [t for t in aux0 if t is not None]
         geo.launch_searches = launch_searches
         if not defer_searches:
             launch_searches()
         return geo
 
     def _geometry_finish(self, geo):
-        """The host's wait for the three level sizes (in flight since the end of the sampling chain, while the searches run)."""
+        """The host's wait for the three level sizes (in flight since the end of the sampling chain, while the searches run).
+        Returns the geometry to use: `geo`, or the one of the repeated pass where a table overflowed."""
         geo.sizes_ready.synchronize()
         ps = geo.pstride
         overflow = [l for l in geo.table_levels if int(geo.counts_host[3 * ps + l])]
@@ -654,22 +730,15 @@ class Engine:
             # the batch's cell grid did not fit the sampler's table at these levels (device-side knowledge): everything
             # downstream of the first of them is undefined.  Repeat the geometry with the sort (rare: voxels much larger than
             # 2 m), and give the table 8 x the room next time.
-            for l in overflow:   # more room next time (capped); whether a batch's table is worth taking is _table_cells' decision
-                if l in getattr(geo, "table_probes", ()):   # a probe below the remembered factor failed: no growth, no probing for a while
-                    self._table_probe_rest[l] = self.TABLE_REST
-                    continue
-                if self._table_scale[l] >= self.TABLE_SCALE_MAX:
-                    self._table_rest[l] = self.TABLE_REST     # no more room to give: the sort serves the next batches
-                self._table_scale[l] = min(self._table_scale[l] * 8, self.TABLE_SCALE_MAX)
-            search_stream = getattr(geo, "search_stream", None)
+            for l in overflow:
+                self._table.overflowed(l, l in geo.table_probes)
             with torch.cuda.stream(geo.stream):
-                if search_stream is not None:       # the discarded searches still read the buffers this Geometry is about to drop
+                if geo.search_stream is not None:   # the discarded searches still read the buffers the old Geometry is about to drop
                     if geo.launch_searches is not None:
                         geo.launch_searches()
                     geo.stream.wait_event(geo.done)
-                redo = self._geometry_async(*geo.args, force_sort=True, search_stream=search_stream)
-            redo.sizes_ready.synchronize()
-            geo.__dict__.update(redo.__dict__)
+                geo = self._geometry_async(*geo.args, force_sort=True, search_stream=geo.search_stream)
+            geo.sizes_ready.synchronize()
         for l in (1, 2, 3):
             geo.levels[l].n = int(geo.counts_host[(l - 1) * geo.pstride + geo.B])
         return geo
@@ -682,13 +751,13 @@ class Engine:
         """Enqueues the feature phase on the current stream.  With the range guard on, ``geo.watch`` then holds the phase's range
         report (in flight on the same stream: ``checked`` evaluates it once the phase has finished)."""
         if self.prec is not None:
-            if getattr(geo, "early", None) is None:      # (an early part has opened the range watch already)
+            if geo.early is None:      # (an early part has opened the range watch already)
                 self._range_begin(geo.sf.device)
             logits = self._features_h2(geo, keep)
             geo.watch = self._range_end()
             return logits
         geo.watch = None
-        if getattr(geo, "search_stream", None) is not None:   # the fp32 parity mode runs behind the searches
+        if geo.search_stream is not None:   # the fp32 parity mode runs behind the searches
             if geo.launch_searches is not None:
                 geo.launch_searches()
             torch.cuda.current_stream().wait_event(geo.done)
@@ -697,16 +766,19 @@ class Engine:
     def checked(self, geo: Geometry, logits, keep: dict | None = None):
         """The range guard's verdict on a FINISHED feature phase (the caller has waited for it): `logits`, or - when a layer's
         outputs left the range the 16-bit planes carry - the logits of ``fallback`` (the fp32 MFMA engine) on the same geometry,
-        enqueued on the current stream.  Silent saturation is never an outcome: without a fallback the forward raises."""
-        bad = self.range_violations(getattr(geo, "watch", None))
+        enqueued on the current stream.  Values beyond +-6e4 are never passed on silently: without a fallback that finding
+        raises.  A finding that is ONLY "no value above 2^-5" comes from a sample: it takes the fallback where one can run
+        (there is one, and level 0 is not kept in cell order); otherwise the logits are returned as computed, with one warning
+        per engine, and nothing raises."""
+        bad = self.range_violations(geo.watch)
         if not bad:
             return logits
         what = "; ".join(f"{n}: {v}" for n, v in bad[:4])
         # "no value above 2^-5" is SAMPLED (wave 0 of every persistent workgroup's first tile): on a small or sparse layer the
         # sample can miss.  It is acted on where a recomputation is available; it never raises by itself.
         sampled_only = all(v.startswith("no value above") for _, v in bad)
-        if sampled_only and (self.fallback is None or getattr(geo, "rows0_sorted", False)):
-            if not getattr(self, "_seen_warned", False):
+        if sampled_only and (self.fallback is None or geo.rows0_sorted):
+            if not self._seen_warned:
                 import warnings
                 self._seen_warned = True
                 warnings.warn(f"pointstowood_amd: precision {self.precision!r}: the range watch saw no value above {self.RANGE_LO:g} in its "
@@ -770,9 +842,7 @@ class Engine:
 
     def _gemm_h2(self, name, A, ldh_a, M, lin: Linear, out_f32=None, ldo=0, out_h2=None, ldh_o=0, residual=None, ldr=0,
                  residual_h=False, watch=None, interp=None):
-        ep = Epilogue(ptr(lin.bias), ptr(lin.sc0), ptr(lin.sh0), ptr(lin.sc1), ptr(lin.sh1), ptr(residual), ldr,
-                      lin.relu0, lin.relu1, lin.relu2, lin.relu_final, self._watch(watch, M),
-                      ptr(interp), 0 if interp is None else residual.shape[0])
+        ep = self._epilogue(lin, residual, ldr, self._watch(watch, M), ptr(interp), 0 if interp is None else residual.shape[0])
         flags = self.gemm_flags | (GEMM_RESIDUAL_H if residual_h else 0)
         if self.gemm_stream_k:
             ws = self._sk_workspace(A.device)
@@ -785,19 +855,16 @@ class Engine:
     def _sk_workspace(self, dev):
         """The stream-K workspace of the CURRENT stream (launches on different streams may overlap, so each stream that runs
         GEMMs owns one; allocated once, p2w_gemm_h2_sk_ws_bytes() = 32 MiB on a 256-CU chip)."""
-        pool = self.__dict__.setdefault("_sk_ws", {})
         key = _lib.stream()
-        ws = pool.get(key)
+        ws = self._sk_ws.get(key)
         if ws is None:
-            ws = pool[key] = torch.empty(int(lib().p2w_gemm_h2_sk_ws_bytes()), dtype=torch.uint8, device=dev)
+            ws = self._sk_ws[key] = torch.empty(int(lib().p2w_gemm_h2_sk_ws_bytes()), dtype=torch.uint8, device=dev)
         return ws
 
     def _hoist(self, xh_src, pitch_src, n_src, p, l):
         """SA level l's hoisted layer-1 product P = x_src W1x^T + b1: n_src rows + one all-zero row (read by empty neighbour slots),
         row pitch padded to whole K slabs with zero columns (p2w_sa_conv_h reads it with unconditional loads)."""
-        ka = 32 if self.prec == PREC_F16X3 else 64
-        C1 = p["C1"]
-        C1p = (C1 + ka - 1) // ka * ka
+        C1, C1p = p["C1"], self.h.pitch(p["C1"])
         P = torch.empty((n_src + 1, C1p), dtype=torch.float32, device=xh_src.device)     # (row n_src: zeroed by p2w_sa_conv_h's pre-pass)
         if C1p != C1:
             P[:, C1:].zero_()
@@ -810,23 +877,17 @@ class Engine:
         L, w = lib(), self.w
         dev = geo.sf.device
         Cw, N, prec = w.C, geo.N, self.prec
-        ka, planes = (32, 2) if prec == PREC_F16X3 else (64, 1)
-        hdt = torch.bfloat16 if self.precision == "bf16" else torch.float16
         F3 = 16 * Cw
-        pitch0 = (F3 + Cw + ka - 1) // ka * ka
-        cat0 = torch.empty((N, planes * pitch0), dtype=hdt, device=dev)      # rows of FP1: [interpolated (16 C) | stem features (C)]
-        xh0 = cat0[:, planes * F3:]
+        pitch0 = self.h.pitch(F3 + Cw)
+        cat0 = self.h.new(N, F3 + Cw, dev)      # rows of FP1: [interpolated (16 C) | stem features (C)]
+        xh0 = self.h.col(cat0, F3)
         x0 = torch.empty((N, Cw), dtype=torch.float32, device=dev)
         # Level 0 in the sampler's CELL ORDER (fp1_cell_order): the H rows of the input points' features - the skip columns of FP1's rows,
         # the A operand of SA1's hoisted product - are row p = the p-th point of the cell-sorted order, so are FP1's rows, its MLP, the head;
         # the logits are scattered back at the end.  Spatial neighbours are then memory neighbours: the last interpolation's two coarse
         # rows per point and SA1's P rows come from L2.  The fp32 stem features (data.x, model.py:228) stay in input order.
-        if bool(getattr(geo, "rows0_sorted", False)):
-            self._call("stem", L.p2w_stem_h2_indexed, prec, ptr(geo.sorted0), N, ptr(w.stem_w), ptr(w.stem_b), Cw, ptr(x0), ptr(xh0),
-                       pitch0, self._watch("stem", N))
-        else:
-            self._call("stem", L.p2w_stem_h2, prec, ptr(geo.levels[0].xyzr), N, ptr(w.stem_w), ptr(w.stem_b), Cw, ptr(x0), ptr(xh0),
-                       pitch0, self._watch("stem", N))
+        stem, rec0 = (L.p2w_stem_h2_indexed, geo.sorted0) if geo.rows0_sorted else (L.p2w_stem_h2, geo.levels[0].xyzr)
+        self._call("stem", stem, prec, ptr(rec0), N, ptr(w.stem_w), ptr(w.stem_b), Cw, ptr(x0), ptr(xh0), pitch0, self._watch("stem", N))
         self.stem_out = x0
         P1 = self._hoist(xh0, pitch0, N, w.sa[0], 1)
         return dict(lv0=geo.levels[0], cat0=cat0, x0=x0, P1=P1)
@@ -846,11 +907,8 @@ class Engine:
         Cw = w.C
         new = lambda r, c: torch.empty((r, c), dtype=torch.float32, device=dev)
         prec = self.prec
-        ka, planes = (32, 2) if prec == PREC_F16X3 else (64, 1)
-        hdt = torch.bfloat16 if self.precision == "bf16" else torch.float16
-        pad8 = lambda f: (f + ka - 1) // ka * ka   # H row pitch: zero-padded to the GEMM's K slab so it can be DMA-staged
-        newh = lambda r, f: torch.empty((r, planes * pad8(f)), dtype=hdt, device=dev)
-        hcol = lambda t, c: t[:, planes * c:]      # view of an H tensor from column c on (c a multiple of the slab width)
+        pad8, hcol = self.h.pitch, self.h.col      # (HLayout)
+        newh = lambda r, f: self.h.new(r, f, dev)
         lv, N, B = geo.levels, geo.N, geo.B
         F3 = 16 * Cw
         res_h = prec == PREC_F16X3                 # residual read from H (the single-plane modes keep their fp32 residual)
@@ -858,24 +916,23 @@ class Engine:
         Fs = [Cw, 4 * Cw, 8 * Cw, 16 * Cw]
         rows = [N, lv[1].n, lv[2].n, lv[3].n]
         pitch = [pad8(F3 + Fs[f]) for f in range(4)]
-        early = getattr(geo, "early", None) or self._features_early(geo)
+        early = geo.early or self._features_early(geo)
         cat = [early["cat0"]] + [newh(rows[f], F3 + Fs[f]) for f in range(1, 4)]
         xh = [hcol(cat[f], F3) for f in range(4)]   # H features of level f = the skip columns of its FP module's rows
         x0 = early["x0"]
-        sorted0 = bool(getattr(geo, "rows0_sorted", False))
+        sorted0 = geo.rows0_sorted
         wait = lambda ev: torch.cuda.current_stream().wait_event(ev) if ev is not None else None   # a search result is about to be read
-        ev_nbr, ev_fp = getattr(geo, "ev_nbr", {}), getattr(geo, "ev_fp", {})
 
         def need(table, key):
             """The search result (table, key) is about to be read: if the staggered forward has not enqueued that search yet, it
             goes out now; then the caller's stream waits for its event."""
-            while table.get(key) is None and getattr(geo, "launch_searches", None) is not None:
+            while table.get(key) is None and geo.launch_searches is not None:
                 geo.launch_searches(1)
             wait(table.get(key))
 
         def stage(count):
             """Staggered lone forward: enqueue the next `count` searches behind the feature kernel just launched."""
-            if getattr(geo, "launch_searches", None) is not None and getattr(geo, "search_stream", None) is not None:
+            if geo.launch_searches is not None and geo.search_stream is not None:
                 ev = torch.cuda.Event()
                 ev.record()
                 geo.launch_searches(count, after=ev)
@@ -885,11 +942,9 @@ class Engine:
         for l in (1, 2, 3):
             p, src, dst = w.sa[l - 1], lv[l - 1], lv[l]
             M, C1, C2, E = dst.n, p["C1"], p["C2"], 4 * p["C2"]
-            # hoisted layer-1 product P = x_src W1x^T + b1: src.n rows + one all-zero row (read by empty neighbour slots), row
-            # pitch padded to whole K slabs with zero columns (p2w_sa_conv_h reads it with unconditional loads)
             C1p = pad8(C1)
-            P = early["P1"] if l == 1 else self._hoist(xh[l - 1], pitch[l - 1], src.n, p, l)
-            need(ev_nbr, l)
+            P = early["P1"] if l == 1 else self._hoist(xh[l - 1], pitch[l - 1], src.n, p, l)   # (row pitch C1p)
+            need(geo.ev_nbr, l)
             conv = new(M, C2) if (keep is not None or not res_h) else None
             convh = newh(M, C2)
             # level 1 is the ball query: on sparse input most targets have few neighbours, and those with <= 8 share an MFMA
@@ -905,38 +960,17 @@ class Engine:
             stage(1 if l < 3 else 2)     # (no-op unless staggered: kNN level 3 behind SA1, interpolation search 2 behind SA2, 1 and 0 behind SA3)
             # fp32 form of the level's output: level 3 feeds cat(x, pos) of the global module; otherwise only on request
             out = new(M, C2) if (keep is not None or l == 3) else None
-            # residual block in row chunks: the two 4F-wide intermediates of a chunk (2 x chunk x 4F x 4 B) are written
-            # and re-read while they still sit in the 256 MiB Infinity Cache instead of round-tripping HBM
-            chunk = self.res_chunk_rows if self.res_chunk_rows > 0 else M
-            chunk = max(256, min(M, pick_chunk(M, chunk * 512 // E, E // 256, full_rounds=self.chunk_full_rounds and not self.gemm_stream_k) if self.chunk_pick
-                                 else (chunk * 512 // E) // 256 * 256))   # ~same bytes per chunk at every level
-            # Chunks are independent chains of four GEMMs; alternating them between two streams lets the tiles of one
-            # chain fill the CUs the other leaves idle at its wave tails (a 1122-row tail chunk at level 3 otherwise
-            # runs four GEMMs at 16 % chip fill).
-            nst = max(1, min(self._chains(), -(-M // chunk)))
-            cur = torch.cuda.current_stream()
-            side = self._side_stream(cur) if nst > 1 else None
-            lanes = [cur] + ([side] if nst > 1 else [])
-            bufs = [(newh(min(M, chunk), E), newh(min(M, chunk), E)) for _ in lanes]
-            if nst > 1:
-                ready = torch.cuda.Event()
-                ready.record(cur)
-                side.wait_event(ready)
-            for ci, r0 in enumerate(range(0, M, chunk)):
-                m = min(chunk, M - r0)
-                (e1, e2), st = bufs[ci % len(lanes)], lanes[ci % len(lanes)]
-                with torch.cuda.stream(st):
-                    self._gemm_h2("gemm_res", convh[r0:], pad8(C2), m, p["g1"], out_h2=e1, ldh_o=pad8(E), watch=f"res{l}.1")
-                    self._gemm_h2("gemm_res", e1, pad8(E), m, p["g2"], out_h2=e2, ldh_o=pad8(E), watch=f"res{l}.2")
-                    self._gemm_h2("gemm_res", e2, pad8(E), m, p["g3"], out_h2=e1, ldh_o=pad8(E), watch=f"res{l}.3")
-                    self._gemm_h2("gemm_res", e1, pad8(E), m, p["g4"], out_f32=None if out is None else out[r0:], ldo=C2,
-                                  out_h2=xh[l][r0:], ldh_o=pitch[l],
-                                  residual=convh[r0:] if res_h else conv[r0:], ldr=pad8(C2) if res_h else C2, residual_h=res_h,
-                                  watch=f"res{l}.4")
-            if nst > 1:   # join: everything after this level (and the buffers' reuse) is ordered behind both chains
-                done = torch.cuda.Event()
-                done.record(side)
-                cur.wait_event(done)
+            # residual block: per chunk a chain of four GEMMs over two 4F-wide intermediates
+            def res_chunk(r0, m, bufs):
+                e1, e2 = bufs
+                self._gemm_h2("gemm_res", convh[r0:], pad8(C2), m, p["g1"], out_h2=e1, ldh_o=pad8(E), watch=f"res{l}.1")
+                self._gemm_h2("gemm_res", e1, pad8(E), m, p["g2"], out_h2=e2, ldh_o=pad8(E), watch=f"res{l}.2")
+                self._gemm_h2("gemm_res", e2, pad8(E), m, p["g3"], out_h2=e1, ldh_o=pad8(E), watch=f"res{l}.3")
+                self._gemm_h2("gemm_res", e1, pad8(E), m, p["g4"], out_f32=None if out is None else out[r0:], ldo=C2,
+                              out_h2=xh[l][r0:], ldh_o=pitch[l],
+                              residual=convh[r0:] if res_h else conv[r0:], ldr=pad8(C2) if res_h else C2, residual_h=res_h,
+                              watch=f"res{l}.4")
+            self._chunk_chains(geo, M, E, E // 256, True, lambda rows: (newh(rows, E), newh(rows, E)), res_chunk)
             if l == 3:
                 x3 = out
             if keep is not None:
@@ -956,13 +990,11 @@ class Engine:
         nbr4 = torch.empty(M3, dtype=torch.int32, device=dev)
         deg4 = torch.empty(M3, dtype=torch.int32, device=dev)
         self._call("fill_batch_nbr", L.p2w_fill_batch_nbr, ptr(lv[3].batch), M3, ptr(nbr4), ptr(deg4))
-        zc = self.__dict__.setdefault("_zeros_c", {})      # the pooled level's positions (model.py:138: zeros): one constant per batch size
+        zc = self._zeros_c      # the pooled level's positions (model.py:138: zeros): one constant per batch size
         if (B, dev) not in zc:
             zc[(B, dev)] = torch.zeros((B, 4), dtype=torch.float32, device=dev)
             torch.cuda.current_stream().synchronize()      # (once per batch size: later phases on other streams read it without an event)
         zeros_c = zc[(B, dev)]
-        # Row-chunked chains: interpolate -> MLP layer 0 -> MLP layer 1 (-> head for fp1) run chunk by chunk so the wide
-        # intermediates of a chunk are consumed out of the Infinity Cache (same trick as the residual blocks).
         y, y_xyzr, y_h = g, zeros_c, None      # coarse features (fp32), their positions, their H form (where the next module hoists)
         y_rows, y_cols = g.shape               # (a module whose successor takes the linearity route leaves no fp32 form)
         logits = torch.empty(N, dtype=torch.float32, device=dev) if w.num_classes == 1 else None
@@ -973,7 +1005,7 @@ class Engine:
             m, Fc, cf, ld = fine.n, y_cols, cat[fl - 1], pitch[fl - 1]
             nbr, deg, kw = (nbr4, deg4, 1) if fl == 4 else (*geo.fp_nbr[fl - 1], 2)
             if fl < 4:
-                need(ev_fp, fl - 1)
+                need(geo.ev_fp, fl - 1)
             fine_xyzr = geo.sorted0 if (fl == 1 and sorted0) else fine.xyzr   # FP1's rows (and fp_nbr[0]'s) are in cell order then
             l0, l1 = w.fp[fl]
             # layer 0's interpolated half on the coarse rows (PackedWeights.fp_split)?  This module: the previous one left the H
@@ -995,59 +1027,41 @@ class Engine:
                 rec = torch.empty((m, 4), dtype=torch.int32, device=dev)
                 self._call("interp_concat", L.p2w_interp_weights, ptr(y_xyzr), ptr(fine_xyzr), ptr(nbr), ptr(deg), kw, m, ptr(rec))
             yh_full = newh(m, l1.N) if next_hoist else None
-            chunk = self.res_chunk_rows if self.res_chunk_rows > 0 else m
-            chunk = max(256, min(m, pick_chunk(m, chunk * 512 // (Fc + Fs[fl - 1]), max(1, l0.N // 256)) if self.chunk_pick
-                                 else (chunk * 512 // (Fc + Fs[fl - 1])) // 256 * 256))
-            mc = min(m, chunk)
             need_f32 = (fl > 1 and not next_hoist) or keep is not None   # (the next module interpolates the fp32 rows unless it hoists)
             b = new(m, l1.N) if need_f32 else None
-            # chunk chains alternate between two streams like the residual blocks' (each lane has its own intermediates)
-            nst = max(1, min(self._chains(), -(-m // chunk)))
-            cur = torch.cuda.current_stream()
-            side = self._side_stream(cur) if nst > 1 else None
-            lanes = [cur] + ([side] if nst > 1 else [])
             # head for one class (model.py:241-243): conv1 + BN + ReLU + conv2 as ONE operator, its [m, 512] intermediate never
             # reaches HBM (p2w_gemm_h2_rowdot: per-slice partial dot products in the GEMM's epilogue + a finishing pass)
             one = fl == 1 and w.num_classes == 1
-            bufs = [dict(a=newh(mc, l0.N), yh=newh(mc, l1.N) if fl == 1 else None,
-                         hws=torch.empty(int(L.p2w_gemm_h2_rowdot_ws_bytes(mc, w.head1.N)), dtype=torch.uint8, device=dev) if one else None,
-                         hdh=newh(mc, F3) if (fl == 1 and not one) else None) for _ in lanes]
-            if nst > 1:
-                ready = torch.cuda.Event()
-                ready.record(cur)
-                side.wait_event(ready)
-            for ci, r0 in enumerate(range(0, m, chunk)):
-                mm = min(chunk, m - r0)
-                bf, st = bufs[ci % len(lanes)], lanes[ci % len(lanes)]
+
+            def fp_bufs(mc):
+                return dict(a=newh(mc, l0.N), yh=newh(mc, l1.N) if fl == 1 else None,
+                            hws=torch.empty(int(L.p2w_gemm_h2_rowdot_ws_bytes(mc, w.head1.N)), dtype=torch.uint8, device=dev) if one else None,
+                            hdh=newh(mc, F3) if (fl == 1 and not one) else None)
+
+            def fp_chunk(r0, mm, bf):
                 a, yh, hws, hdh = bf["a"], bf["yh"], bf["hws"], bf["hdh"]
-                with torch.cuda.stream(st):
-                    if hoist:   # relu(W_s skip + b + interp(W_i y)): the interpolation of Z's rows happens in the epilogue
-                        self._gemm_h2("gemm_mlp", xh[fl - 1][r0:], ld, mm, ls, out_h2=a, ldh_o=pad8(l0.N), residual=Z, ldr=l0.N,
-                                      interp=rec[r0:], watch=f"fp{fl}.0")
-                    else:
-                        # the interpolated part only (skip = NULL): the skip columns of these rows were written by their producer
-                        self._call("interp_concat", L.p2w_interp_concat_h2, prec, ptr(y), Fc, ptr(y_xyzr), ptr(fine_xyzr[r0:]),
-                                   ptr(nbr[r0:]), ptr(deg[r0:]), kw, None, 0, mm, ptr(cf[r0:]), ld)
-                        self._gemm_h2("gemm_mlp", cf[r0:], ld, mm, l0, out_h2=a, ldh_o=pad8(l0.N), watch=f"fp{fl}.0")
-                    if yh_full is not None:
-                        yh = yh_full[r0:]
-                    self._gemm_h2("gemm_mlp", a, pad8(l0.N), mm, l1, out_f32=None if b is None else b[r0:], ldo=l1.N,
-                                  out_h2=yh, ldh_o=pad8(l1.N), watch=f"fp{fl}.1")
-                    if fl == 1:   # head (model.py:241-243) on the same chunk
-                        if one:
-                            lin = w.head1
-                            ep = Epilogue(ptr(lin.bias), ptr(lin.sc0), ptr(lin.sh0), ptr(lin.sc1), ptr(lin.sh1), None, 0,
-                                          lin.relu0, lin.relu1, lin.relu2, lin.relu_final)
-                            self._call("gemm_mlp", L.p2w_gemm_h2_rowdot, prec, ptr(yh), pad8(F3), ptr(lin.w16), lin.wscale, mm, lin.N,
-                                       lin.K, C.byref(ep), ptr(w.head2_w), float(w.head2_b[0]), ptr(logits[r0:]), ptr(hws),
-                                       hws.numel(), self.gemm_flags)
-                        else:   # multi-class head: conv2 is one more (narrow) GEMM over the H form of conv1's output
-                            self._gemm_h2("gemm_mlp", yh, pad8(F3), mm, w.head1, out_h2=hdh, ldh_o=pad8(F3), watch="head1")
-                            self._gemm_h2("gemm_mlp", hdh, pad8(F3), mm, w.head2, out_f32=o_multi[r0:], ldo=w.num_classes)
-            if nst > 1:   # join
-                done = torch.cuda.Event()
-                done.record(side)
-                cur.wait_event(done)
+                if hoist:   # relu(W_s skip + b + interp(W_i y)): the interpolation of Z's rows happens in the epilogue
+                    self._gemm_h2("gemm_mlp", xh[fl - 1][r0:], ld, mm, ls, out_h2=a, ldh_o=pad8(l0.N), residual=Z, ldr=l0.N,
+                                  interp=rec[r0:], watch=f"fp{fl}.0")
+                else:
+                    # the interpolated part only (skip = NULL): the skip columns of these rows were written by their producer
+                    self._call("interp_concat", L.p2w_interp_concat_h2, prec, ptr(y), Fc, ptr(y_xyzr), ptr(fine_xyzr[r0:]),
+                               ptr(nbr[r0:]), ptr(deg[r0:]), kw, None, 0, mm, ptr(cf[r0:]), ld)
+                    self._gemm_h2("gemm_mlp", cf[r0:], ld, mm, l0, out_h2=a, ldh_o=pad8(l0.N), watch=f"fp{fl}.0")
+                if yh_full is not None:
+                    yh = yh_full[r0:]
+                self._gemm_h2("gemm_mlp", a, pad8(l0.N), mm, l1, out_f32=None if b is None else b[r0:], ldo=l1.N,
+                              out_h2=yh, ldh_o=pad8(l1.N), watch=f"fp{fl}.1")
+                if one:   # head (model.py:241-243) on the same chunk
+                    lin, ep = w.head1, self._epilogue(w.head1)
+                    self._call("gemm_mlp", L.p2w_gemm_h2_rowdot, prec, ptr(yh), pad8(F3), ptr(lin.w16), lin.wscale, mm, lin.N,
+                               lin.K, C.byref(ep), ptr(w.head2_w), float(w.head2_b[0]), ptr(logits[r0:]), ptr(hws),
+                               hws.numel(), self.gemm_flags)
+                elif fl == 1:   # multi-class head: conv2 is one more (narrow) GEMM over the H form of conv1's output
+                    self._gemm_h2("gemm_mlp", yh, pad8(F3), mm, w.head1, out_h2=hdh, ldh_o=pad8(F3), watch="head1")
+                    self._gemm_h2("gemm_mlp", hdh, pad8(F3), mm, w.head2, out_f32=o_multi[r0:], ldo=w.num_classes)
+            # interpolate -> MLP layer 0 -> MLP layer 1 (-> head for fp1), chunk by chunk like the residual blocks
+            self._chunk_chains(geo, m, Fc + Fs[fl - 1], max(1, l0.N // 256), False, fp_bufs, fp_chunk)
             y, y_xyzr, y_h = b, fine.xyzr, yh_full
             y_rows, y_cols = m, l1.N
             if keep is not None:
@@ -1149,7 +1163,7 @@ class Engine:
         product and the first searches; every feature kernel that reads a search result waits for that search's event.  Results
         are those of the sequential order, bit for bit."""
         overlap = bool(self.overlap) and self.events is None
-        search_stream = self._search_stream() if overlap else None
+        search_stream = self._companion(self._search_streams, self.search_priority) if overlap else None
         geo = self._geometry_async(pos, reflectance, ptr0, sf, search_stream=search_stream, defer_searches=overlap)
         early = None
         if not self.early_first and geo.launch_searches is not None:
@@ -1163,33 +1177,21 @@ class Engine:
             # search_stagger: the ball query and the level-2 kNN now; the level-3 kNN and the interpolation searches are enqueued by
             # the feature phase where it wants them to start (each behind the PointNetConv of the level before)
             geo.launch_searches(2 if (overlap and self.search_stagger and self.prec is not None) else None)
-        self._geometry_finish(geo)
+        geo = self._geometry_finish(geo)
         if early is not None and early["lv0"] is not geo.levels[0]:   # (the table overflowed and the geometry was redone: level 0 is new)
             early = None
         if keep is not None:
             keep["geometry"] = geo
             if keep.get("geometry_only"):   # profiling: the level sizes are wanted, the fp32 copies of the level features are not
                 keep = None
-        geo.early = early
-        self._lone = self.events is None
-        try:
-            logits = self.features(geo, keep)
-        finally:
-            self._lone = False
+        geo.early, geo.lone = early, self.events is None
+        logits = self.features(geo, keep)
         if geo.search_stream is not None:     # nothing of this forward is left on the side stream when the caller gets its logits
             torch.cuda.current_stream().wait_event(geo.done)
         if geo.watch is not None:   # the range guard needs the finished phase: one more host wait per forward (Net.stream hides it)
             torch.cuda.current_stream().synchronize()
             logits = self.checked(geo, logits, keep)
         return logits
-
-    def _search_stream(self):
-        """The side stream of the single-call forward's searches (one per caller stream)."""
-        pool = self.__dict__.setdefault("_search_streams", {})
-        key = _lib.stream()
-        if key not in pool:
-            pool[key] = torch.cuda.Stream(priority=int(self.search_priority))
-        return pool[key]
 
     # -- two-stream software pipeline over a sequence of batches ---------------------------------------------
     def forward_stream(self, inputs):
@@ -1200,7 +1202,7 @@ class Engine:
         results.  The only host wait per batch is for the three level sizes of the NEXT batch's geometry, which has
         been running concurrently."""
         cur_stream = torch.cuda.current_stream()
-        if getattr(self, "_s_geo", None) is None:
+        if self._s_geo is None:
             # The feature phase is the critical path (9 of 10 ms) and its MFMA kernels leave no room on a CU for anything
             # else, so IT gets the high-priority stream and the geometry of the next batch fills what is left (next to
             # the PointNetConv kernels, at kernel tails): measured 10.09 vs 10.23 ms per step against the opposite
@@ -1208,9 +1210,7 @@ class Engine:
             self._s_geo = torch.cuda.Stream(priority=int(self.geo_priority))
             self._s_feat = [torch.cuda.Stream(priority=int(self.feat_priority))
                             for _ in range(max(1, self.feature_streams))]
-        s_geo = self._s_geo
-        f_streams = self._s_feat[: max(1, self.feature_streams)]
-        yield from self._forward_stream(inputs, cur_stream, s_geo, f_streams)
+        yield from self._forward_stream(inputs, cur_stream, self._s_geo, self._s_feat[: max(1, self.feature_streams)])
 
     def _forward_stream(self, inputs, cur_stream, s_geo, f_streams):
 
@@ -1218,12 +1218,11 @@ class Engine:
             s_geo.wait_stream(cur_stream)
             for t in args:
                 # the inputs were allocated on the caller's stream (possibly by a just-issued H2D copy or a dtype
-                # conversion in Net._inputs) and are read on s_geo: the allocator must not recycle them under it
+                # conversion in Net._inputs) and are read on s_geo: the allocator must not recycle them under it (geo.args keeps
+                # them alive until this batch's features were launched, Geometry.tensors() has them recorded on that stream too)
                 t.record_stream(s_geo)
             with torch.cuda.stream(s_geo):
-                geo = self._geometry_async(*args)
-            geo.aux = list(geo.aux) + list(args)   # ... and they stay alive until this batch's features were launched
-            return geo
+                return self._geometry_async(*args)
 
         def finish(logits, ev, g, fs):
             """Hand a batch's logits to the caller's stream; with the range guard, after the host has seen the phase finish and
@@ -1254,7 +1253,7 @@ class Engine:
         i = 0
         while geo is not None:
             nxt = next(it, None)
-            self._geometry_finish(geo)                    # host waits for THIS batch's level sizes only
+            geo = self._geometry_finish(geo)              # host waits for THIS batch's level sizes only
             geo_next = launch_geometry(nxt) if nxt is not None else None
             fs = f_streams[i % len(f_streams)]
             fs.wait_event(geo.done)

@@ -133,7 +133,7 @@ class Net(torch.nn.Module):
         """The feature phase of `geo` on the fp32 MFMA path: what the range guard (EngineOptions.range_guard) runs instead when a
         layer's activations do not fit the 16-bit planes of f16x3 / fp16 / bf16 (a checkpoint whose BatchNorm scales push them
         beyond +-6e4 or under fp16's subnormal floor).  The geometry is precision-independent and is reused."""
-        if getattr(geo, "rows0_sorted", False):
+        if geo.rows0_sorted:
             raise RuntimeError("range fallback: not available with fp1_cell_order=True (the fp32 path keeps level 0 in input order)")
         dev = geo.sf.device
         if self._fb_engine is None or self._fb_engine.w.device != dev:

@@ -240,6 +240,24 @@ def test_stream_pipeline_equals_sequential_forward():
         own = [net2(mk(b)).clone() for b in batches]       # (another chunking plans other split-K tails: last fp32 bits may differ
         assert len(got) == 11 and all(torch.equal(a, own[i % 4]) for i, a in enumerate(got)), kw   # from `seq`, never from `own`)
         assert all((a - seq[i % 4]).abs().max() <= 2e-4 for i, a in enumerate(got)), kw
+    # the table sampler's overflow redo INSIDE the pipeline (the geometry of that batch is replaced while the next one's is being
+    # launched): a fresh engine whose first call is the stream, the oversized batch (three 4 m voxels) in it twice
+    big = synth.collate([synth.uniform_voxel(4.0, 6000, 190 + i, True) for i in range(3)])
+    mixed = [batches[0], big, batches[1], big]
+    nets = []
+    for _ in range(2):
+        nets.append(Net(num_classes=1, C=8, k=32))
+        nets[-1].load_state_dict(weights.synth_state_dict(1, 8, seed=5), strict=True)
+        nets[-1] = nets[-1].cuda().eval()
+    got = [o.clone() for o in nets[0].stream(mk(b) for b in mixed)]
+    torch.cuda.synchronize()
+    # level 0 of that batch takes the sort by itself (3 x 216 000 cells > 32 per point x 18 000 points); level 1's table holds
+    # 31 cells of 0.08 m per axis and voxel, a 4 m voxel spans 50: that level overflows
+    print("table scale after the stream:", nets[0]._engine._table_scale)
+    assert nets[0]._engine._table_scale[1] >= 8              # (it was 1: the redo ran in the stream)
+    own = [nets[1](mk(b)).clone() for b in mixed]
+    torch.cuda.synchronize()
+    assert len(got) == 4 and all(torch.equal(a, b) for a, b in zip(got, own))
 
 
 def test_lone_forward_with_searches_beside_the_features_is_bit_identical():
@@ -616,7 +634,7 @@ def test_forward_fuzz_against_live_oracle(seed):
         n = geo.levels[f].n
         ours = nbr[:n].cpu().long().clone()
         ours[torch.arange(2)[None, :] >= deg[:n].cpu().long()[:, None]] = -1
-        if f == 0 and getattr(geo, "rows0_sorted", False):   # level 0's rows are kept in the sampler's cell order (fp1_cell_order)
+        if f == 0 and geo.rows0_sorted:   # level 0's rows are kept in the sampler's cell order (fp1_cell_order)
             unsorted = torch.empty_like(ours)
             unsorted[geo.order[:n].cpu().long()] = ours
             ours = unsorted

@@ -725,6 +725,46 @@ def test_pick_chunk_properties():
     assert pick_chunk(131072, 61680, 2) == 65536                                               # FP1: two full chunks, no 8192-row tail
 
 
+def test_table_provision_policy():
+    """The table sampler's provisioning (engine.TableProvision) as host arithmetic: when the table is taken, the x 8 growth after
+    an overflow, the rest period at the largest scale, probing below the remembered factor.  Expected values: the policy as it
+    stood inside the engine, default options (32 cells per point, capacity 2^26, scale cap 64, rest 64)."""
+    from pointstowood_amd.engine import EngineOptions, TableProvision
+    fresh = lambda **kw: TableProvision(EngineOptions(**kw))
+    N = 131072
+    t = fresh()
+    assert (t.CELLS_MAX, t.SCALE_MAX, t.REST) == (1 << 26, 64, 64)
+    assert [t.cells(l, 8, N) for l in (0, 1, 2)] == [(1728000, False), (238328, False), (39304, False)]
+    assert [t.cells(l, 300, N) for l in (0, 1, 2)] == [(0, False), (0, False), (1473900, False)]   # too many cells per point: the sort
+    assert (t.scale, t.rest, t.probe_rest) == ([1, 1, 1], [0, 0, 0], [0, 0, 0])
+    s = fresh(sampler="sort")
+    assert all(s.cells(l, B, N) == (0, False) for l in (0, 1, 2) for B in (1, 8, 300))
+    # one overflow: x 8; levels are independent
+    t.overflowed(0, False)
+    assert t.scale == [8, 1, 1] and t.cells(0, 8, N) == (13824000, False)
+    assert [t.cells(l, 8, N) for l in (1, 2)] == [(238328, False), (39304, False)]
+    # a second one: scale 64, where the same batch no longer fits and probes at factor 8
+    t.overflowed(0, False)
+    assert t.scale == [64, 1, 1] and t.cells(0, 8, N) == (13824000, True)
+    # an overflow at the largest scale: the scale stays, the level rests for 64 calls, then answers again
+    t.overflowed(0, False)
+    assert t.scale == [64, 1, 1] and t.rest == [64, 0, 0]
+    assert all(t.cells(0, 8, N) == (0, False) for _ in range(64))
+    assert t.cells(0, 8, N) == (13824000, True)
+    assert [t.cells(l, 8, N) for l in (1, 2)] == [(238328, False), (39304, False)] and t.scale[1:] == [1, 1] and t.rest[1:] == [0, 0]
+    # scale 8, many nominal voxels: a probe; a failed probe does not grow the factor and silences probing for 64 such batches
+    p = fresh()
+    p.overflowed(0, False)
+    assert p.cells(0, 48, 336000) == (10368000, True)
+    p.overflowed(0, True)
+    assert p.scale == [8, 1, 1] and p.rest == [0, 0, 0]
+    for _ in range(64):
+        assert p.cells(0, 48, 336000) == (0, False)
+        assert p.cells(0, 8, N) == (13824000, False)      # a batch that fits at the remembered scale is served unaffected
+    assert p.cells(0, 48, 336000) == (10368000, True)
+    assert p.scale == [8, 1, 1] and p.probe_rest[1:] == [0, 0]
+
+
 def test_concurrent_lazy_builds_serialise(tmp_path):
     """Every rank of a torch.distributed.run launch may find the library stale at once (``*.so`` is not in git): exactly
     one of them must build, under the lock, and the others must come back with the fresh library."""

@@ -117,7 +117,7 @@ def main():
     # knn_interpolate of FP4..FP1 (model.py:149): coarse -> fine, k = 2 (FP4: the voxel's one global row, k = 1)
     for name, f in (("FP4", 3), ("FP3", 2), ("FP2", 1), ("FP1", 0)):
         m = M[f]
-        rf = (geo.sorted0 if f == 0 and getattr(geo, "rows0_sorted", False) else lv[f].xyzr)[:m].contiguous()   # the rows fp_nbr[0] is in
+        rf = (geo.sorted0 if f == 0 and geo.rows0_sorted else lv[f].xyzr)[:m].contiguous()   # the rows fp_nbr[0] is in
         if f == 3:
             nc, kw = geo.B, 1
             nbr, dg = lv[3].batch[:m].to(torch.int32).reshape(m, 1).contiguous(), torch.ones(m, dtype=torch.int32, device=dev)
