@@ -1,10 +1,11 @@
 // The plot-level cell grid on the device (plotgrid.build on the host: p2w_voxel_sample's cell-sorted keys and p2w_grid,
-// p2w_cell_starts' table), shared by p2w_cluster.hip and p2w_pathlen.hip: the run of the sorted order that holds a cell, the
-// cell coordinates of a key, and the relaxed agent-scope loads both files read their shared words with.
+// p2w_cell_starts' table), shared by p2w_cluster.hip, p2w_pathlen.hip and p2w_geom.hip (the grid searches' run tables and
+// knn_refine_kernel): the run of the sorted order that holds a cell, the cell coordinates of a key, and the relaxed agent-scope
+// loads the first two files read their shared words with.
 //
-// Not included by p2w_geom.hip, whose lower_bound_key and knn_refine_kernel lookup do the same: that file has to stay byte
-// for byte as it is, because bench.py --full accepts the recorded evaluated-pair counts (profiles/r6_search_evaluated.json)
-// only for its sha256, and the counts can only be regenerated with a diagnostic build.
+// (bench.py --full accepts the recorded evaluated-pair counts, profiles/r6_search_evaluated.json, only for the sha256 of
+// p2w_geom.hip: an edit of that file - not of this header - needs the counts regenerated with a -DP2W_SLAB_PROFILE build,
+// tools/slab_prof.py --json.)
 #pragma once
 #include "p2w_common.h"
 

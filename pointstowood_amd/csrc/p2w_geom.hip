@@ -1,5 +1,6 @@
 // Geometry kernels: record packing, grid sub-sampling, level gather, ball query, exact kNN.
 // gfx950 only (wave64, LDS-staged candidate tiles, wave-level ballot/popcount selection).
+#include "p2w_cells.h"
 #include "p2w_common.h"
 #include "p2w_sort.h"
 #include <cstdlib>
@@ -744,7 +745,12 @@ extern "C" int32_t p2w_level_gather(const float* xyzr_src, const int32_t* idx, c
 // ------------------------------------------------------------------------------------------------
 constexpr int S_QPW = 8;             // queries per wave
 constexpr int S_QT = 4 * S_QPW;      // queries per workgroup
-constexpr int S_TILE = 1024;         // candidates per LDS stage (16 KiB)
+constexpr int S_TILE = 1024;         // candidates per LDS stage (16 KiB): the brute-force kernels, and the grid kernels for k < 8 and ball queries
+#ifndef P2W_KNN_TILE
+#define P2W_KNN_TILE 1792            // candidates per LDS stage of the k >= 8 searches (a multiple of 256; the typical k = 32 region holds ~1200).
+                                     // 1792 and not 2048: 28 KiB + run tables fit BESIDE a 256 x 256 GEMM workgroup's 128 KiB on a CU (2048: 162 KiB
+                                     // of 160) - searches run next to feature kernels; same search time, lone forward -0.6 %, pipelined -0.4 %
+#endif
 
 // blockIdx -> (voxel b, first query q0, end q1).  Tiles never straddle voxels.
 // Query tile of a workgroup.  Voxel b owns the virtual tiles [V(b), V(b + 1)), V(b) = ptr_q[b] / S_QT + b: at least
@@ -786,28 +792,131 @@ __device__ __forceinline__ UQuery load_query(const float4* __restrict__ xq, cons
     return u;
 }
 
-__device__ __forceinline__ void stage_candidates(float4* cand, const float4* __restrict__ x, int base, int c1, int tid) {
-#pragma unroll
-    for (int r = 0; r < S_TILE / 256; ++r) {
-        const int c = base + tid + 256 * r;
-        cand[tid + 256 * r] = (c < c1) ? x[c] : make_float4(INFINITY, INFINITY, INFINITY, 0.f);
-    }
-}
-
-// Staging permutes the records of a tile (slot s holds candidate base + ((s * 389) & 1023)) so that every
-// 64-slot chunk samples the whole tile: levels >= 1 are stored in grid-cell order, and a scan in storage order
-// approaches each query monotonically, which makes almost every candidate a new admission.  The candidate's
-// index travels in the record's 4th component; admission is order-independent (lexicographic (d2, index)).
-__device__ __forceinline__ void stage_shuffled(float4* cand, const float4* __restrict__ x, int base, int c1, int tid,
-                                               bool index_in_w) {
+// Stages one tile; the candidate's index travels in the record's 4th component, empty slots hold (+inf, INT_MAX).
+// SHUFFLE permutes the records of the tile (slot s holds candidate base + ((s * 389) & 1023)) so that every 64-slot chunk
+// samples the whole tile: levels >= 1 are stored in grid-cell order, and a scan in storage order approaches each query
+// monotonically, which makes almost every candidate a new kNN admission.  Admission is order-independent (lexicographic
+// (d2, index)); the ball query, which admits by index alone, stages in storage order.
+template <bool SHUFFLE>
+__device__ __forceinline__ void stage_tile(float4* cand, const float4* __restrict__ x, int base, int c1, int tid, bool index_in_w) {
 #pragma unroll
     for (int r = 0; r < S_TILE / 256; ++r) {
         const int s = tid + 256 * r;
-        const int c = base + ((s * 389) & (S_TILE - 1));
+        const int c = base + (SHUFFLE ? (s * 389) & (S_TILE - 1) : s);
         float4 v = make_float4(INFINITY, INFINITY, INFINITY, __int_as_float(0x7fffffff));
         if (c < c1) { v = x[c]; if (!index_in_w) v.w = __int_as_float(c); }
         cand[s] = v;
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Selection: what the brute-force kernels and the grid kernel keep of the candidates they are shown.  One copy, so that
+// "the grid search equals the brute-force one bit for bit" is a statement about which candidates are shown, not about two
+// insertion routines.  Everything here is wave-uniform control flow over per-lane list slots.
+// ------------------------------------------------------------------------------------------------
+// kNN: lane l of (bd, bi) = the l-th smallest (d2, index) pair so far; empty slots and lanes >= k hold (+inf, INT_MAX); t = the
+// wave-uniform admission bound.  Every lane offers its candidate (d, ci); those with d <= t are inserted one by one.
+// t = fminf(t, slot k-1): the bound may have been seeded below the list's own k-th distance (hint, threshold ladder) and must
+// not be raised by an insertion.  From a cold start (t = +inf) this equals t = slot k-1: that slot is +inf until k pairs are
+// kept and only ever decreases afterwards, so the minimum with the previous bound is the slot itself.
+__device__ __forceinline__ void knn_admit(float d, int ci, int k, bool in_k, int lane, float& bd, int& bi, float& t) {
+    unsigned long long m = __ballot(d <= t);
+    // (unlikely: once the list is warm almost every 64 candidates admit nothing, and that path should fall through)
+    while (__builtin_expect(m != 0ull, 0)) {  // wave-uniform loop over the candidates that may enter
+        const int src = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const float dn = rdlane(d, src);
+        const int in = __builtin_amdgcn_readlane(ci, src);
+        // (d2, index) pairs order like the 64-bit integers (bits(d2) << 32 | index): d2 >= +0, index >= 0.
+        // pos = number of kept pairs below the new one; it enters iff pos < k
+        const unsigned long long kn = ((unsigned long long)__float_as_uint(dn) << 32) | (unsigned)in;
+        const unsigned long long kb = ((unsigned long long)__float_as_uint(bd) << 32) | (unsigned)bi;
+        const int pos = __popcll(__ballot(kb < kn));
+        if (pos < k) {  // scalar branch
+            const float up_d = shr1(bd);
+            const int up_i = shr1(bi);
+            const bool here = lane == pos, sh = (lane > pos) & in_k;
+            bd = here ? dn : (sh ? up_d : bd);
+            bi = here ? in : (sh ? up_i : bi);
+            t = fminf(t, rdlane(bd, k - 1));
+        }
+    }
+}
+
+// Ball query: lane l of bi = the l-th smallest in-ball index so far (INT_MAX = empty); ti = wave-uniform copy of slot cap-1.
+// Every lane offers its candidate's index ci, `hit` says whether it lies in the ball.
+__device__ __forceinline__ void ball_admit(bool hit, int ci, int cap, bool in_cap, int lane, int& bi, int& ti) {
+    unsigned long long m = __ballot(hit && ci < ti);
+    while (m) {
+        const int src = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const int in = __builtin_amdgcn_readlane(ci, src);
+        if (in < ti) {
+            const int pos = __popcll(__ballot(bi < in));
+            const int up_i = shr1(bi);
+            bi = (lane == pos) ? in : (((lane > pos) & in_cap) ? up_i : bi);
+            ti = __builtin_amdgcn_readlane(bi, cap - 1);
+        }
+    }
+}
+
+// A staged tile against the wave's queries (qmask: the wave-uniform set of queries that still take part).  kNN: groups of 4
+// chunks (256 candidates) are held in registers while the wave walks its queries, so the per-query state is in scalars inside the
+// admission loop.  The arrays are the callers' registers: everything unrolls.
+__device__ __forceinline__ void scan_knn(const float4* cand, int groups, unsigned qmask, const UQuery (&uq)[S_QPW],
+                                         float (&best_d)[S_QPW], int (&best_i)[S_QPW], float (&thr)[S_QPW], int k, bool in_k,
+                                         int lane) {
+    for (int gr = 0; gr < groups; ++gr) {
+        float4 c[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) c[u] = cand[gr * 256 + u * 64 + lane];
+#pragma unroll
+        for (int j = 0; j < S_QPW; ++j) {
+            if (!((qmask >> j) & 1u)) continue;   // wave-uniform
+            float bd = best_d[j], t = thr[j];
+            int bi = best_i[j];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                knn_admit(p2w_d2(uq[j].x, uq[j].y, uq[j].z, c[u].x, c[u].y, c[u].z), __float_as_int(c[u].w), k, in_k, lane, bd, bi, t);
+            best_d[j] = bd; best_i[j] = bi; thr[j] = t;
+        }
+    }
+}
+
+// Ball query: single chunks; cnt counts every in-ball candidate, admitted or not.
+__device__ __forceinline__ void scan_ball(const float4* cand, int nch, unsigned qmask, const UQuery (&uq)[S_QPW], float r2,
+                                          int (&best_i)[S_QPW], int (&thi)[S_QPW], int (&cnt)[S_QPW], int cap, bool in_cap,
+                                          int lane) {
+    for (int ch = 0; ch < nch; ++ch) {
+        const float4 c = cand[ch * 64 + lane];
+#pragma unroll
+        for (int j = 0; j < S_QPW; ++j) {
+            if (!((qmask >> j) & 1u)) continue;   // wave-uniform
+            const bool hit = p2w_d2(uq[j].x, uq[j].y, uq[j].z, c.x, c.y, c.z) < r2;
+            const unsigned long long mh = __ballot(hit);
+            if (mh == 0ull) continue;
+            cnt[j] += __popcll(mh);
+            ball_admit(hit, __float_as_int(c.w), cap, in_cap, lane, best_i[j], thi[j]);
+        }
+    }
+}
+
+// "forget what you hold": the empty selection state of one query, both modes' (knn_admit, ball_admit)
+__device__ __forceinline__ void forget_query(float& bd, int& bi, float& t, int& ti, int& cnt) {
+    bd = INFINITY; bi = 0x7fffffff; t = INFINITY; ti = 0x7fffffff; cnt = 0;
+}
+
+// One query's row of the neighbour table: the list's first `kept` slots, -1 behind them, and the degree.  kept is clamped to
+// the slots that were really filled: a query with NaN coordinates admits nothing, and an unset slot is never reported.  (For
+// the ball query kept = min(cnt, cap) is that number already - every in-ball candidate is admitted while the list has room, and
+// a NaN query has cnt == 0 - so the clamp changes nothing there.)
+__device__ __forceinline__ void write_neighbours(int* __restrict__ nbr, int* __restrict__ deg, const float4* __restrict__ xq,
+                                                 const int* __restrict__ qidx, int q, int flags, int k, int kept, int best_i,
+                                                 int lane) {
+    const int row = (flags & P2W_SEARCH_Q_ROW_IN_W) ? __float_as_int(xq[qidx ? qidx[q] : q].w) : q;
+    kept = min(kept, __popcll(__ballot(best_i != 0x7fffffff)));
+    if (lane < k) nbr[(size_t)row * k + lane] = (lane < kept) ? best_i : -1;
+    if (lane == 0) deg[row] = kept;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -878,22 +987,48 @@ extern "C" int32_t p2w_tile_bbox(const float* xyzr, const int32_t* ptr, int32_t 
 }
 extern "C" int32_t p2w_tile_bbox_count(int32_t B, int32_t n_bound) { return p2w_cdiv(n_bound, S_TILE) + B; }
 
+// Squared gap between a point and a tile's box (lo xyz, hi xyz), the bound behind the exact pruning: per dimension e = gap
+// between the point and the box; ((ex^2+ey^2)+ez^2) in fp32 is a lower bound of p2w_d2(point, c) for every c in the tile
+// (fp32 subtract / multiply / add are monotone, and this is p2w_d2's own order of operations), so a tile whose bound exceeds
+// a query's current k-th distance (or reaches r2) cannot change that query's result.
+__device__ __forceinline__ float box_gap2(const float* __restrict__ box6, float x, float y, float z) {
+    const float ex = fmaxf(fmaxf(box6[0] - x, x - box6[3]), 0.f);
+    const float ey = fmaxf(fmaxf(box6[1] - y, y - box6[4]), 0.f);
+    const float ez = fmaxf(fmaxf(box6[2] - z, z - box6[5]), 0.f);
+    return ((ex * ex) + (ey * ey)) + (ez * ez);
+}
+
 // start tile of a workgroup whose queries are not candidates: the tile whose box is nearest to the first query (box gap
 // first, then distance to the box centre).  Only the visiting order depends on this, never a result.
 __device__ __forceinline__ int nearest_tile(const float* __restrict__ vb, int ntiles, const float4 f) {
     float best_lb = INFINITY, best_c = INFINITY;
     int t0 = 0;
     for (int t = 0; t < ntiles; ++t) {
-        const float lx = vb[t * 6 + 0], ly = vb[t * 6 + 1], lz = vb[t * 6 + 2];
-        const float hx = vb[t * 6 + 3], hy = vb[t * 6 + 4], hz = vb[t * 6 + 5];
-        const float ex = fmaxf(fmaxf(lx - f.x, f.x - hx), 0.f), ey = fmaxf(fmaxf(ly - f.y, f.y - hy), 0.f);
-        const float ez = fmaxf(fmaxf(lz - f.z, f.z - hz), 0.f);
-        const float lb = ex * ex + ey * ey + ez * ez;
-        const float cx = 0.5f * (lx + hx) - f.x, cy = 0.5f * (ly + hy) - f.y, cz = 0.5f * (lz + hz) - f.z;
+        const float* box = vb + t * 6;
+        const float lb = box_gap2(box, f.x, f.y, f.z);
+        const float cx = 0.5f * (box[0] + box[3]) - f.x, cy = 0.5f * (box[1] + box[4]) - f.y, cz = 0.5f * (box[2] + box[5]) - f.z;
         const float cd = cx * cx + cy * cy + cz * cz;
         if (lb < best_lb || (lb == best_lb && cd < best_c)) { best_lb = lb; best_c = cd; t0 = t; }
     }
     return t0;
+}
+
+// the step-th tile of the walk outwards from t0 (t0, t0 + 1, t0 - 1, t0 + 2, ...), -1 where that lies outside [0, ntiles)
+__device__ __forceinline__ int walk_tile(int t0, int step, int ntiles) {
+    const int off = (step + 1) >> 1;
+    const int tile = (step & 1) ? t0 + off : t0 - off;
+    return (tile < 0 || tile >= ntiles) ? -1 : tile;
+}
+
+// Does any wave of the workgroup want the next tile (`mine`: this wave does)?  Holds the barrier that also says "the previous
+// tile is consumed", so every wave calls it for every tile; without boxes (vote false) every tile is wanted.  Two sets of
+// flags, used alternately: a wave may vote on the next tile while another still reads this one's flags.
+__device__ __forceinline__ bool tile_wanted(int (&need)[2][4], int& visit, bool vote, bool mine, int wave, int lane) {
+    if (vote && lane == 0) need[visit & 1][wave] = mine;
+    __syncthreads();
+    if (!vote) return true;
+    const int* n = need[visit++ & 1];
+    return (n[0] | n[1] | n[2] | n[3]) != 0;
 }
 
 __global__ __launch_bounds__(256) void knn_kernel(const float4* __restrict__ x, const int* __restrict__ ptr_x,
@@ -910,9 +1045,7 @@ __global__ __launch_bounds__(256) void knn_kernel(const float4* __restrict__ x, 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int qw = q0 + wave * S_QPW;
     UQuery uq[S_QPW];
-    // selection state: lane l of (best_d, best_i)[j] = the l-th smallest (d2, index) so far of query j;
-    // empty slots and lanes >= k hold (+inf, INT_MAX); thr = wave-uniform copy of slot k-1's distance
-    float best_d[S_QPW], thr[S_QPW];
+    float best_d[S_QPW], thr[S_QPW];   // selection state (knn_admit); thr = -inf: nothing is ever admitted for an unused slot
     int best_i[S_QPW];
 #pragma unroll
     for (int j = 0; j < S_QPW; ++j) {
@@ -931,96 +1064,28 @@ __global__ __launch_bounds__(256) void knn_kernel(const float4* __restrict__ x, 
     if (vb && !qidx_is_candidate) t0 = nearest_tile(vb, ntiles, xq[qidx ? qidx[q0] : q0]);   // queries of another level
     int visit = 0;
     for (int step = 0; step < 2 * ntiles - 1; ++step) {
-        const int off = (step + 1) >> 1;
-        const int tile = (step & 1) ? t0 + off : t0 - off;
-        if (tile < 0 || tile >= ntiles) continue;
-        const int base = c0 + tile * S_TILE;
-        // exact pruning: per dimension e = gap between the query and the tile's box; ((ex^2+ey^2)+ez^2) in fp32 is a
-        // lower bound of p2w_d2(query, c) for every c in the tile (fp32 subtract / multiply / add are monotone), so a
-        // tile whose bound exceeds a query's current k-th distance cannot change that query's result.
+        const int tile = walk_tile(t0, step, ntiles);
+        if (tile < 0) continue;
         unsigned qmask = (1u << S_QPW) - 1u;
-        if (vb) {
-            const float lx = vb[tile * 6 + 0], ly = vb[tile * 6 + 1], lz = vb[tile * 6 + 2];
-            const float hx = vb[tile * 6 + 3], hy = vb[tile * 6 + 4], hz = vb[tile * 6 + 5];
+        if (vb) {   // the queries whose k-th distance the tile's box can still undercut
             qmask = 0u;
 #pragma unroll
-            for (int j = 0; j < S_QPW; ++j) {
-                const float ex = fmaxf(fmaxf(lx - uq[j].x, uq[j].x - hx), 0.f);
-                const float ey = fmaxf(fmaxf(ly - uq[j].y, uq[j].y - hy), 0.f);
-                const float ez = fmaxf(fmaxf(lz - uq[j].z, uq[j].z - hz), 0.f);
-                const float lb = ((ex * ex) + (ey * ey)) + (ez * ez);
-                if (lb <= thr[j]) qmask |= 1u << j;
-            }
-            if (lane == 0) need[visit & 1][wave] = qmask != 0u;
+            for (int j = 0; j < S_QPW; ++j)
+                if (box_gap2(vb + tile * 6, uq[j].x, uq[j].y, uq[j].z) <= thr[j]) qmask |= 1u << j;
         }
+        if (!tile_wanted(need, visit, vb != nullptr, qmask != 0u, wave, lane)) continue;   // skip staging it
+        stage_tile<true>(cand, x, c0 + tile * S_TILE, c1, tid, (flags & P2W_SEARCH_X_INDEX_IN_W) != 0);
         __syncthreads();
-        if (vb) {
-            const int any = need[visit & 1][0] | need[visit & 1][1] | need[visit & 1][2] | need[visit & 1][3];
-            ++visit;
-            if (!any) continue;   // no query of this workgroup can gain from the tile: skip staging it
-        }
-        stage_shuffled(cand, x, base, c1, tid, (flags & P2W_SEARCH_X_INDEX_IN_W) != 0);
-        __syncthreads();
-        // groups of 4 chunks (256 candidates) are held in registers while the wave walks its queries, so the
-        // per-query state is in scalars inside the admission loop
-        const int ngr = (min(S_TILE, c1 - base) + 255) >> 8;
-        for (int gr = 0; gr < S_TILE / 256; ++gr) {   // all groups: the shuffle spreads a partial tile over every group
-            float4 c[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) c[u] = cand[gr * 256 + u * 64 + lane];
-#pragma unroll
-            for (int j = 0; j < S_QPW; ++j) {
-                if (!((qmask >> j) & 1u)) continue;   // wave-uniform
-                float bd = best_d[j], t = thr[j];
-                int bi = best_i[j];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float d = p2w_d2(uq[j].x, uq[j].y, uq[j].z, c[u].x, c[u].y, c[u].z);
-                    const int ci = __float_as_int(c[u].w);
-                    unsigned long long m = __ballot(d <= t);
-                    while (m) {  // wave-uniform loop over the candidates that may enter
-                        const int src = __ffsll((long long)m) - 1;
-                        m &= m - 1;
-                        const float dn = rdlane(d, src);
-                        const int in = __builtin_amdgcn_readlane(ci, src);
-                        // (d2, index) pairs order like the 64-bit integers (bits(d2) << 32 | index): d2 >= +0, index >= 0.
-                        // pos = number of kept pairs below the new one; it enters iff pos < k
-                        const unsigned long long kn = ((unsigned long long)__float_as_uint(dn) << 32) | (unsigned)in;
-                        const unsigned long long kb = ((unsigned long long)__float_as_uint(bd) << 32) | (unsigned)bi;
-                        const int pos = __popcll(__ballot(kb < kn));
-                        if (pos < k) {  // scalar branch
-                            const float up_d = shr1(bd);
-                            const int up_i = shr1(bi);
-                            const bool here = lane == pos, sh = (lane > pos) & in_k;
-                            bd = here ? dn : (sh ? up_d : bd);
-                            bi = here ? in : (sh ? up_i : bi);
-                            t = rdlane(bd, k - 1);
-                        }
-                    }
-                }
-                best_d[j] = bd; best_i[j] = bi; thr[j] = t;
-            }
-        }
-        (void)ngr;
+        scan_knn(cand, S_TILE / 256, qmask, uq, best_d, best_i, thr, k, in_k, lane);   // all groups: the shuffle spreads a partial tile over every group
     }
-    const int cnt = min(k, c1 - c0);
 #pragma unroll
-    for (int j = 0; j < S_QPW; ++j) {
-        const int q = qw + j;
-        if (q < q1) {
-            const int row = (flags & P2W_SEARCH_Q_ROW_IN_W) ? __float_as_int(xq[qidx ? qidx[q] : q].w) : q;
-            const int kept = min(cnt, __popcll(__ballot(best_i[j] != 0x7fffffff)));   // NaN query: nothing was admitted
-            if (lane < k) nbr[(size_t)row * k + lane] = (lane < kept) ? best_i[j] : -1;
-            if (lane == 0) deg[row] = kept;
-        }
-    }
+    for (int j = 0; j < S_QPW; ++j)
+        if (qw + j < q1) write_neighbours(nbr, deg, xq, qidx, qw + j, flags, k, min(k, c1 - c0), best_i[j], lane);
 }
 
 // Ball query: the `cap` in-ball candidates (d2 < r2) with the smallest reported indices, ascending - which is
-// torch-cluster's "first cap hits in index order" whatever order the candidates are stored or visited in.  Lane l of
-// best_i[j] = the l-th smallest in-ball index so far of query j (INT_MAX = empty); thi = wave-uniform copy of slot
-// cap-1.  With tile boxes, tiles farther than r from every query of the workgroup are never staged (exact: the box
-// gap is a lower bound of p2w_d2 under fp32 rounding).
+// torch-cluster's "first cap hits in index order" whatever order the candidates are stored or visited in (selection state:
+// ball_admit).  With tile boxes, tiles farther than r from every query of the workgroup are never staged (box_gap2).
 __global__ __launch_bounds__(256) void ball_kernel(const float4* __restrict__ x, const int* __restrict__ ptr_x,
                                                    const float4* __restrict__ xq, const int* __restrict__ qidx,
                                                    const int* __restrict__ ptr_q, int B, float r2, int cap,
@@ -1034,15 +1099,16 @@ __global__ __launch_bounds__(256) void ball_kernel(const float4* __restrict__ x,
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int qw = q0 + wave * S_QPW;
-    const bool index_in_w = (flags & P2W_SEARCH_X_INDEX_IN_W) != 0;
     UQuery uq[S_QPW];
     int best_i[S_QPW], thi[S_QPW], cnt[S_QPW];
+    unsigned valid = 0u;
 #pragma unroll
     for (int j = 0; j < S_QPW; ++j) {
         uq[j] = load_query(xq, qidx, qw + j, q1);
         best_i[j] = 0x7fffffff;
         thi[j] = uq[j].valid ? 0x7fffffff : -1;   // -1: nothing is ever admitted for an unused slot
         cnt[j] = 0;
+        valid |= uq[j].valid ? (1u << j) : 0u;
     }
     const bool in_cap = lane < cap;
     const int ntiles = (c1 - c0 + S_TILE - 1) / S_TILE;
@@ -1050,85 +1116,26 @@ __global__ __launch_bounds__(256) void ball_kernel(const float4* __restrict__ x,
     const int t0 = vb ? nearest_tile(vb, ntiles, xq[qidx ? qidx[q0] : q0]) : 0;
     int visit = 0;
     for (int step = 0; step < 2 * ntiles - 1; ++step) {
-        const int off = (step + 1) >> 1;
-        const int tile = (step & 1) ? t0 + off : t0 - off;
-        if (tile < 0 || tile >= ntiles) continue;
+        const int tile = walk_tile(t0, step, ntiles);
+        if (tile < 0) continue;
         const int base = c0 + tile * S_TILE;
-        unsigned qmask = 0u;
-#pragma unroll
-        for (int j = 0; j < S_QPW; ++j) qmask |= uq[j].valid ? (1u << j) : 0u;
-        if (vb) {
-            const float lx = vb[tile * 6 + 0], ly = vb[tile * 6 + 1], lz = vb[tile * 6 + 2];
-            const float hx = vb[tile * 6 + 3], hy = vb[tile * 6 + 4], hz = vb[tile * 6 + 5];
+        unsigned qmask = valid;
+        if (vb) {   // the queries whose ball reaches the tile's box
             unsigned near = 0u;
 #pragma unroll
-            for (int j = 0; j < S_QPW; ++j) {
-                const float ex = fmaxf(fmaxf(lx - uq[j].x, uq[j].x - hx), 0.f);
-                const float ey = fmaxf(fmaxf(ly - uq[j].y, uq[j].y - hy), 0.f);
-                const float ez = fmaxf(fmaxf(lz - uq[j].z, uq[j].z - hz), 0.f);
-                const float lb = ((ex * ex) + (ey * ey)) + (ez * ez);
-                if (lb < r2) near |= 1u << j;
-            }
+            for (int j = 0; j < S_QPW; ++j)
+                if (box_gap2(vb + tile * 6, uq[j].x, uq[j].y, uq[j].z) < r2) near |= 1u << j;
             qmask &= near;
-            if (lane == 0) need[visit & 1][wave] = qmask != 0u;
         }
+        if (!tile_wanted(need, visit, vb != nullptr, qmask != 0u, wave, lane)) continue;
+        stage_tile<false>(cand, x, base, c1, tid, (flags & P2W_SEARCH_X_INDEX_IN_W) != 0);
         __syncthreads();
-        if (vb) {
-            const int any = need[visit & 1][0] | need[visit & 1][1] | need[visit & 1][2] | need[visit & 1][3];
-            ++visit;
-            if (!any) continue;
-        }
-#pragma unroll
-        for (int r = 0; r < S_TILE / 256; ++r) {
-            const int c = base + tid + 256 * r;
-            float4 v = make_float4(INFINITY, INFINITY, INFINITY, __int_as_float(0x7fffffff));
-            if (c < c1) { v = x[c]; if (!index_in_w) v.w = __int_as_float(c); }
-            cand[tid + 256 * r] = v;
-        }
-        __syncthreads();
-        const int nch = (min(S_TILE, c1 - base) + 63) >> 6;
-        for (int ch = 0; ch < nch; ++ch) {
-            const float4 c = cand[ch * 64 + lane];
-            const int ci = __float_as_int(c.w);
-#pragma unroll
-            for (int j = 0; j < S_QPW; ++j) {
-                if (!((qmask >> j) & 1u)) continue;   // wave-uniform
-                const float d = p2w_d2(uq[j].x, uq[j].y, uq[j].z, c.x, c.y, c.z);
-                const bool hit = d < r2;
-                const unsigned long long mh = __ballot(hit);
-                if (mh == 0ull) continue;
-                cnt[j] += __popcll(mh);
-                unsigned long long m = __ballot(hit && ci < thi[j]);
-                int bi = best_i[j], ti = thi[j];
-                while (m) {
-                    const int src = __ffsll((long long)m) - 1;
-                    m &= m - 1;
-                    const int in = __builtin_amdgcn_readlane(ci, src);
-                    if (in < ti) {
-                        const int pos = __popcll(__ballot(bi < in));
-                        const int up_i = shr1(bi);
-                        bi = (lane == pos) ? in : (((lane > pos) & in_cap) ? up_i : bi);
-                        ti = __builtin_amdgcn_readlane(bi, cap - 1);
-                    }
-                }
-                best_i[j] = bi; thi[j] = ti;
-            }
-        }
+        scan_ball(cand, (min(S_TILE, c1 - base) + 63) >> 6, qmask, uq, r2, best_i, thi, cnt, cap, in_cap, lane);
     }
 #pragma unroll
-    for (int j = 0; j < S_QPW; ++j) {
-        const int q = qw + j;
-        if (q < q1) {
-            const int row = (flags & P2W_SEARCH_Q_ROW_IN_W) ? __float_as_int(xq[qidx ? qidx[q] : q].w) : q;
-            const int kept = min(cnt[j], cap);
-            if (lane < cap) nbr[(size_t)row * cap + lane] = (lane < kept) ? best_i[j] : -1;
-            if (lane == 0) deg[row] = kept;
-        }
-    }
+    for (int j = 0; j < S_QPW; ++j)
+        if (qw + j < q1) write_neighbours(nbr, deg, xq, qidx, qw + j, flags, cap, min(cnt[j], cap), best_i[j], lane);
 }
-
-
-
 
 // ------------------------------------------------------------------------------------------------
 // grid-indexed neighbour search
@@ -1137,7 +1144,7 @@ __global__ __launch_bounds__(256) void ball_kernel(const float4* __restrict__ x,
 // holds their keys.  A workgroup still owns 32 consecutive queries of one voxel, but instead of streaming the whole
 // voxel it gathers only the rows of the grid within a radius rho of its queries' bounding box: for every z layer the
 // rows [Ylo, Yhi] are one contiguous run of the storage order, found with two binary searches on the keys.  The runs
-// are concatenated into LDS tiles and scanned exactly like the brute-force kernels do.
+// are concatenated into LDS tiles and scanned by the brute-force kernels' own scan_knn / scan_ball.
 //   ball query: rho = r, one pass.
 //   kNN       : rho starts from a local density estimate; after a pass every query checks that its k-th distance is
 //               not larger than its distance to the nearest face of the gathered region (rows outside it can only hold
@@ -1147,21 +1154,6 @@ __global__ __launch_bounds__(256) void ball_kernel(const float4* __restrict__ x,
 // is provably farther than the accepted k-th distance (or than r), so the result equals the brute-force one bit for bit.
 // ------------------------------------------------------------------------------------------------
 constexpr int G_MAXRUN = 256;        // runs per pass (2 per z layer)
-#ifndef P2W_KNN_TILE
-#define P2W_KNN_TILE 1792            // candidates per LDS stage of the k >= 8 searches (a multiple of 256; the typical k = 32 region holds ~1200).
-                                     // 1792 and not 2048: 28 KiB + run tables fit BESIDE a 256 x 256 GEMM workgroup's 128 KiB on a CU (2048: 162 KiB
-                                     // of 160) - searches run next to feature kernels; same search time, lone forward -0.6 %, pipelined -0.4 %
-#endif
-
-__device__ __forceinline__ int lower_bound_key(const unsigned long long* __restrict__ keys, int lo, int hi,
-                                               unsigned long long key) {
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (keys[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // cell index of coordinate v on one axis, clamped to [0, dim-1]
 __device__ __forceinline__ int grid_cell(float v, float lo, float res, long long dim) {
     const float f = floorf((v - lo) / res);
@@ -1221,16 +1213,15 @@ __global__ __launch_bounds__(256, 1) void slab_search_kernel(const float4* __res
     const float eps = res * (1.f / 32.f) + 1e-5f * amax;
 
     UQuery uq[S_QPW];
-    float best_d[S_QPW], thr[S_QPW];
-    int best_i[S_QPW], cnt[S_QPW];
+    float best_d[S_QPW], thr[S_QPW];            // selection state: knn_admit (thr also holds the hints and the ladder's bounds),
+    int best_i[S_QPW], thi[S_QPW], cnt[S_QPW];   // ball_admit; the arrays of the other MODE are dead and cost no registers
     unsigned active = 0u;   // queries of this wave whose result is not final yet
     float xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY, zmin = INFINITY, zmax = -INFINITY;
     float hmax = 0.f, hinted = (MODE == 0 && hint) ? 1.f : 0.f;   // largest hint / every query of the workgroup has one
 #pragma unroll
     for (int j = 0; j < S_QPW; ++j) {
         uq[j] = load_query(xq, qidx, qw + j, q1);
-        best_d[j] = INFINITY; best_i[j] = 0x7fffffff; cnt[j] = 0;
-        thr[j] = MODE == 0 ? INFINITY : __int_as_float(0x7fffffff);   // ball: thr holds the index threshold's bits
+        forget_query(best_d[j], best_i[j], thr[j], thi[j], cnt[j]);
         if (uq[j].valid) {
             active |= 1u << j;
             if (MODE == 0 && hint) {   // caller's upper bound of this query's k-th distance (checked after the first pass)
@@ -1320,8 +1311,8 @@ __global__ __launch_bounds__(256, 1) void slab_search_kernel(const float4* __res
                 // keys (14 dependent loads for a 16 k-point voxel: the run tables were most of a k = 2 search's time)
                 // (clamped to the voxel's range: a sampler call whose grid did not fit its table leaves the table unwritten -
                 // the level is empty then, c0 == c1, and the caller repeats the geometry; nothing may be read through garbage)
-                const int s0 = cell_start ? min(max(cell_start[ka], c0), c1) : lower_bound_key(keys, c0, c1, ka);
-                const int s1 = cell_start ? min(max(cell_start[kz], s0), c1) : lower_bound_key(keys, s0, c1, kz);
+                const int s0 = cell_start ? min(max(cell_start[ka], c0), c1) : cells_lower_bound(keys, c0, c1, ka);
+                const int s1 = cell_start ? min(max(cell_start[kz], s0), c1) : cells_lower_bound(keys, s0, c1, kz);
                 run_start[tid] = s0;
                 len = s1 - s0;
             }
@@ -1378,12 +1369,8 @@ __global__ __launch_bounds__(256, 1) void slab_search_kernel(const float4* __res
             // the region outgrew the run budget (or the pass budget): the whole voxel is scanned as one run, including
             // what was scanned before, so the unfinished queries start again from scratch
 #pragma unroll
-            for (int j = 0; j < S_QPW; ++j) {
-                if ((active >> j) & 1u) {
-                    best_d[j] = INFINITY; best_i[j] = 0x7fffffff; cnt[j] = 0;
-                    thr[j] = MODE == 0 ? INFINITY : __int_as_float(0x7fffffff);
-                }
-            }
+            for (int j = 0; j < S_QPW; ++j)
+                if ((active >> j) & 1u) forget_query(best_d[j], best_i[j], thr[j], thi[j], cnt[j]);
         }
         for (int rb = 0; rb < nrt; rb += G_MAXRUN) {
         const int n_c = build(rb);
@@ -1466,72 +1453,8 @@ __global__ __launch_bounds__(256, 1) void slab_search_kernel(const float4* __res
                 }
             }
             SLAB_STAMP(6);   // (ladder, when taken; else ~0)
-            if (MODE == 0) {
-                for (int gr = 0; gr < (tsz >> 8); ++gr) {
-                    float4 c[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) c[u] = cand[gr * 256 + u * 64 + lane];
-#pragma unroll
-                    for (int j = 0; j < S_QPW; ++j) {
-                        if (!((active >> j) & 1u)) continue;   // wave-uniform
-                        float bd = best_d[j], t = thr[j];
-                        int bi = best_i[j];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const float d = p2w_d2(uq[j].x, uq[j].y, uq[j].z, c[u].x, c[u].y, c[u].z);
-                            const int ci = __float_as_int(c[u].w);
-                            unsigned long long m = __ballot(d <= t);
-                            while (m) {
-                                const int src = __ffsll((long long)m) - 1;
-                                m &= m - 1;
-                                const float dn = rdlane(d, src);
-                                const int in = __builtin_amdgcn_readlane(ci, src);
-                                const unsigned long long kn = ((unsigned long long)__float_as_uint(dn) << 32) | (unsigned)in;
-                                const unsigned long long kbst = ((unsigned long long)__float_as_uint(bd) << 32) | (unsigned)bi;
-                                const int pos = __popcll(__ballot(kbst < kn));
-                                if (pos < k) {
-                                    const float up_d = shr1(bd);
-                                    const int up_i = shr1(bi);
-                                    const bool here = lane == pos, sh = (lane > pos) & in_k;
-                                    bd = here ? dn : (sh ? up_d : bd);
-                                    bi = here ? in : (sh ? up_i : bi);
-                                    t = fminf(t, rdlane(bd, k - 1));   // slot k-1 is +inf until k pairs are kept
-                                }
-                            }
-                        }
-                        best_d[j] = bd; best_i[j] = bi; thr[j] = t;
-                    }
-                }
-            } else {
-                const int nch = (min(TILE, n_c - tbase) + 63) >> 6;
-                for (int ch = 0; ch < nch; ++ch) {
-                    const float4 c = cand[ch * 64 + lane];
-                    const int ci = __float_as_int(c.w);
-#pragma unroll
-                    for (int j = 0; j < S_QPW; ++j) {
-                        if (!((active >> j) & 1u)) continue;
-                        const float d = p2w_d2(uq[j].x, uq[j].y, uq[j].z, c.x, c.y, c.z);
-                        const bool hit = d < r2;
-                        const unsigned long long mh = __ballot(hit);
-                        if (mh == 0ull) continue;
-                        cnt[j] += __popcll(mh);
-                        int bi = best_i[j], ti = __float_as_int(thr[j]);
-                        unsigned long long m = __ballot(hit && ci < ti);
-                        while (m) {
-                            const int src = __ffsll((long long)m) - 1;
-                            m &= m - 1;
-                            const int in = __builtin_amdgcn_readlane(ci, src);
-                            if (in < ti) {
-                                const int pos = __popcll(__ballot(bi < in));
-                                const int up_i = shr1(bi);
-                                bi = (lane == pos) ? in : (((lane > pos) & in_k) ? up_i : bi);
-                                ti = __builtin_amdgcn_readlane(bi, k - 1);
-                            }
-                        }
-                        best_i[j] = bi; thr[j] = __int_as_float(ti);
-                    }
-                }
-            }
+            if (MODE == 0) scan_knn(cand, tsz >> 8, active, uq, best_d, best_i, thr, k, in_k, lane);
+            else scan_ball(cand, (min(TILE, n_c - tbase) + 63) >> 6, active, uq, r2, best_i, thi, cnt, k, in_k, lane);
         }
         }
         if (!was_whole) { oXlo = nXlo; oXhi = nXhi; oYlo = nYlo; oYhi = nYhi; oZlo = nZlo; oZhi = nZhi; }
@@ -1556,7 +1479,7 @@ __global__ __launch_bounds__(256, 1) void slab_search_kernel(const float4* __res
                 oXlo = 0; oXhi = -1; oYlo = 0; oYhi = -1; oZlo = 0; oZhi = -1;
 #pragma unroll
                 for (int j = 0; j < S_QPW; ++j)
-                    if ((active >> j) & 1u) { best_d[j] = INFINITY; best_i[j] = 0x7fffffff; thr[j] = INFINITY; }
+                    if ((active >> j) & 1u) forget_query(best_d[j], best_i[j], thr[j], thi[j], cnt[j]);   // (kNN mode: cnt and thi are not in use)
             }
         }
         // which queries are final?  k-th distance <= distance to the nearest face of the scanned region
@@ -1590,19 +1513,9 @@ __global__ __launch_bounds__(256, 1) void slab_search_kernel(const float4* __res
         rho = fmaxf(need, rho);
     }
     SLAB_COUNT(11, 1);
-    const int kept_max = min(k, total);
 #pragma unroll
-    for (int j = 0; j < S_QPW; ++j) {
-        const int q = qw + j;
-        if (q < q1) {
-            const int row = (flags & P2W_SEARCH_Q_ROW_IN_W) ? __float_as_int(xq[qidx ? qidx[q] : q].w) : q;
-            int kept = MODE == 0 ? kept_max : min(cnt[j], k);
-            // a query with NaN coordinates admits nothing: report what was really found, never an unset slot
-            kept = min(kept, __popcll(__ballot(best_i[j] != 0x7fffffff)));
-            if (lane < k) nbr[(size_t)row * k + lane] = (lane < kept) ? best_i[j] : -1;
-            if (lane == 0) deg[row] = kept;
-        }
-    }
+    for (int j = 0; j < S_QPW; ++j)
+        if (qw + j < q1) write_neighbours(nbr, deg, xq, qidx, qw + j, flags, k, MODE == 0 ? min(k, total) : min(cnt[j], k), best_i[j], lane);
 }
 
 static int32_t search_args(const float* xyzr_x, const int32_t* ptr_x, const float* xyzr_q, const int32_t* ptr_q, int32_t B,
@@ -1697,7 +1610,6 @@ extern "C" int32_t p2w_ball_query(const float* xyzr_x, const int32_t* ptr_x, con
     return P2W_LAUNCH_STATUS();
 }
 
-
 static int32_t grid_args(const uint64_t* keys, const p2w_grid* grid, int32_t flags) {
     P2W_CHECK_PTR(keys); P2W_CHECK_PTR(grid);
     if ((reinterpret_cast<uintptr_t>(keys) & 7u) || (reinterpret_cast<uintptr_t>(grid) & 7u)) return P2W_EALIGN;
@@ -1749,8 +1661,6 @@ extern "C" int32_t p2w_ball_query_grid(const float* xyzr_x, const uint64_t* keys
                                        p2w_stream_t stream) {
     return p2w_ball_query_grid_indexed(xyzr_x, keys_x, ptr_x, grid, nullptr, xyzr_q, qidx, ptr_q, B, m_bound, r, cap, nbr, deg, flags, stream);
 }
-
-
 
 // Upper bound of the 2nd-nearest-candidate distance of every fine point from the sampler's own bookkeeping: the point's
 // cell representative (rank[i]) is one coarse point, the representative of the nearest point in storage order (same
@@ -2168,9 +2078,7 @@ __global__ __launch_bounds__(256) void knn_refine_kernel(const double* __restric
     }
     const int ny = hi_c[1] - lo_c[1] + 1, nz = hi_c[2] - lo_c[2] + 1;
     const long long rows = (long long)ny * nz;
-    auto start = [&](unsigned long long key) {
-        return cell_start ? cell_start[key] : lower_bound_key(keys, 0, nc, key);
-    };
+    const CellGrid cells{keys, cell_start, nc, g.dims[0], g.dims[1], g.dims[2]};
     // visit(p, d, act): every candidate position p of the rows the ball touches, lanes in lockstep.  A lane owns a grid row (its run
     // [a, b) of the cell-sorted candidates); the runs are FLATTENED through a per-wave LDS list (each lane writes its run's
     // positions behind the wave's running total), so that consecutive lanes then measure consecutive candidates of a run:
@@ -2182,9 +2090,9 @@ __global__ __launch_bounds__(256) void knn_refine_kernel(const double* __restric
             int a = 0, b = 0;
             if (t < rows) {
                 const long long cy = lo_c[1] + t % ny, cz = lo_c[2] + t / ny;
-                const unsigned long long base = (unsigned long long)((cz * g.dims[1] + cy) * g.dims[0]);
-                a = start(base + lo_c[0]);
-                b = start(base + hi_c[0] + 1);
+                const long long base = (cz * g.dims[1] + cy) * g.dims[0];
+                a = cells.start(base + lo_c[0]);
+                b = cells.start(base + hi_c[0] + 1);
             }
             const int len = b - a;
             int pre = len;                                   // inclusive scan of the run lengths over the wave

@@ -659,7 +659,7 @@ def test_hot_kernels_stay_off_the_register_cliff():
             if m:
                 name = m.group(1)
                 usage[name] = {}
-            for key in ("VGPRs Spill", "ScratchSize [bytes/lane]", "VGPRs", "LDS Size [bytes/block]"):
+            for key in ("VGPRs Spill", "ScratchSize [bytes/lane]", "VGPRs", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]"):
                 m = re.search(re.escape(key) + r": (\d+)", line)
                 if m and name:
                     usage[name].setdefault(key, int(m.group(1)))
@@ -676,9 +676,15 @@ def test_hot_kernels_stay_off_the_register_cliff():
         for k in (f"sa_conv16p_kernelILi{prec}ELi256ELi2ELi32E", f"sa_conv16p_kernelILi{prec}ELi128ELi2ELi32E",
                   f"sa_conv16p_kernelILi{prec}ELi256ELi2ELi8E", f"sa_conv16p_kernelILi{prec}ELi128ELi2ELi8E"):
             assert one(k)["VGPRs Spill"] == 0 and one(k)["LDS Size [bytes/block]"] <= 120 * 1024
-    for k, v in usage.items():
-        if "slab_search_kernel" in k or k.startswith("_Z10knn_kernel") or k.startswith("_Z11ball_kernel"):
-            assert v["VGPRs Spill"] == 0, (k, v)
+    # the exact searches: no spill, no scratch, and never fewer resident waves per SIMD than when their code was single-sourced
+    waves = {"_Z10knn_kernel": 7, "_Z11ball_kernel": 7,
+             "slab_search_kernelILi0ELi1792ELi1ELb1E": 4, "slab_search_kernelILi0ELi1024ELi0ELb1E": 5,     # kNN, k >= 8 / k < 8, BOX
+             "slab_search_kernelILi0ELi1792ELi1ELb0E": 4, "slab_search_kernelILi0ELi1024ELi0ELb0E": 6,
+             "slab_search_kernelILi1ELi1024ELi0ELb1E": 6, "slab_search_kernelILi1ELi1024ELi0ELb0E": 6}     # ball query
+    for k, floor in waves.items():
+        v = one(k)
+        assert v["VGPRs Spill"] == 0 and v["ScratchSize [bytes/lane]"] == 0 and v["Occupancy [waves/SIMD]"] >= floor, (k, v)
+    assert sum("slab_search_kernel" in k for k in usage) == 6, [k for k in usage if "slab_search_kernel" in k]
 
 
 def test_feature_kernels_have_no_build_switches():
@@ -703,7 +709,7 @@ def test_plot_grid_is_built_in_one_place():
     assert callers["p2w_cell_starts("] == {"plotgrid.py"}
     assert {"plotgrid.py"} <= callers["p2w_voxel_sample("] <= {"engine.py", "plotgrid.py"}      # (engine.py: its per-batch grids)
     bounds = []
-    for src in ("p2w_cluster.hip", "p2w_pathlen.hip", "p2w_cells.h"):
+    for src in ("p2w_cluster.hip", "p2w_pathlen.hip", "p2w_geom.hip", "p2w_cells.h"):
         text = open(os.path.join(pkg, "csrc", src)).read()
         bounds += [(src, name) for name in re.findall(r"__device__[^;{()]*?\b(\w*lower_bound\w*)\s*\(", text)]
     assert len(bounds) == 1 and bounds[0][0] == "p2w_cells.h", bounds
