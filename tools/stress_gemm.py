@@ -8,8 +8,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
-from test_gpu_ops import H_TOL, _from_h, _pack_h, _to_h  # noqa: E402
+from tests.h_util import H_TOL, _from_h, _pack_h, _to_h  # noqa: E402
 from pointstowood_amd._lib import Epilogue, check, lib, ptr, stream  # noqa: E402
 
 cases, seed = int(sys.argv[1]) if len(sys.argv) > 1 else 150, int(sys.argv[2]) if len(sys.argv) > 2 else 0
