@@ -595,6 +595,40 @@ int32_t p2w_interp_bwd(const float* grad_out, int32_t ldg, int32_t F, const floa
                        const int32_t* deg, int32_t kw, int32_t m, int32_t n_coarse, float* grad_x, int32_t ldx, void* ws,
                        size_t ws_bytes, p2w_stream_t stream);
 
+/* ---- layer 1 of the PointNetConv edge MLP for training (pointstowood_amd/ops.py: edge_layer1) ---- */
+/* The hoisted layer 1 of local_nn per edge (pointnet.py:116-132, model.py:198-202).  The caller computes P[n_src, C1] (pitch ldp) =
+ * x_src W1[:, :F_in]^T + b1 once per source; the edges are grouped by target: ptr[M + 1] is the CSR over the targets (ptr[0] = 0,
+ * ptr[M] = E, any degree), src[E] the source of each edge.  rec_src[n_src, 4] / rec_dst[M, 4] = x, y, z, reflectance;
+ * Wg[4, C1] (dense) = the rows of W1's last four columns.  For edge e = (j -> i), in fp32:
+ *   geo[e, 0:3] = (pos_j - pos_i) / (maxd_i + 1e-8), maxd_i = max over i's edges of sqrt(((dx*dx)+(dy*dy))+(dz*dz));  geo[e, 3] = refl_j
+ *   H1[e, c]    = relu((((P[j, c] + geo0 Wg[0, c]) + geo1 Wg[1, c]) + geo2 Wg[2, c]) + geo3 Wg[3, c])       (pitch ldh; no fma)
+ * geo[E, 4] is dense.  A target all of whose neighbours coincide with it gets geo[:, 0:3] = 0 exactly.  The kernel clamps ptr to
+ * [0, E], and an edge whose source is outside [0, n_src) gets geo = 0 and H1 = 0, so no index is followed out of bounds; rows of
+ * geo / H1 that no target's range covers are not written.  One launch; M = 0 or E = 0 launches nothing.
+ * Access width: C1 a multiple of 4 -> 16 bytes per lane, and then ldp, ldh must be multiples of 4 and P, Wg, H1 16-byte aligned
+ * (P2W_EALIGN otherwise); any other C1 -> 4 bytes per lane.  rec_src, rec_dst and geo are always 16-byte aligned (P2W_EALIGN).
+ * n_src, M, E >= 0, C1 >= 1, ldp, ldh >= C1, E = 0 where M = 0 or n_src = 0 (P2W_EINVAL). */
+int32_t p2w_edge_l1(const float* P, int32_t ldp, const float* rec_src, const float* rec_dst, const int32_t* ptr, const int32_t* src,
+                    const float* Wg, int32_t n_src, int32_t M, int32_t E, int32_t C1, float* geo, float* H1, int32_t ldh,
+                    p2w_stream_t stream);
+/* Its backward.  With gZ[e, c] = (H1[e, c] > 0) ? gH[e, c] : 0 (H1 and geo as the forward left them):
+ *   gP[s, 0:C1]  = sum of gZ[e, :] over the edges with src[e] == s, for every s < n_src (pitch ldgp; no reference: zeros)
+ *   gR[s]        = sum_c gP[s, c] Wg[3, c]  = the gradient with respect to the source's reflectance (no reference: 0)
+ *   gWg[d, c]    = sum_e geo[e, d] gZ[e, c]                                                    (dense [4, C1])
+ * Positions get no gradient.  No floating-point atomics, the same bits on every run: the edges are transposed by source with
+ * p2w_sort_pairs_u64 (stable: a source's edges stay ascending) and p2w_cell_starts, and a source's run is summed like a row of
+ * p2w_interp_bwd (ascending edge order over the row lanes of a block, a tree fixed by the sizes); gR adds gP's columns lane by
+ * lane and the lanes in a fixed butterfly; gWg adds the edges of each chunk of P2W_EDGE_CHUNK edges over row lanes and a tree,
+ * and a second launch adds the chunks in ascending order.  An edge whose source is outside [0, n_src) enters no sum of gP.
+ * Every element of gP[0 .. n_src), gR and gWg is written: the caller clears nothing.  Widths and alignment as in the forward
+ * (gH, H1, gP, gWg and ldg, ldh, ldgp with C1 a multiple of 4; geo and ws always: P2W_EALIGN); sizes as in the forward
+ * (P2W_EINVAL); ws: p2w_edge_l1_bwd_ws_bytes(E, n_src, C1) bytes (0 = bad sizes; too small: P2W_EWORKSPACE). */
+#define P2W_EDGE_CHUNK 1024
+size_t p2w_edge_l1_bwd_ws_bytes(int32_t E, int32_t n_src, int32_t C1);
+int32_t p2w_edge_l1_bwd(const float* gH, int32_t ldg, const float* H1, int32_t ldh, const float* geo, const int32_t* src,
+                        const float* Wg, int32_t n_src, int32_t E, int32_t C1, float* gP, int32_t ldgp, float* gR, float* gWg, void* ws,
+                        size_t ws_bytes, p2w_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

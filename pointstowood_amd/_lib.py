@@ -33,6 +33,7 @@ CLUSTER_LINK, CLUSTER_COMPRESS, CLUSTER_NUMBER, CLUSTER_ALL = 1, 2, 4, 7        
 MAX_K_WIDE = 100                                                                                   # P2W_MAX_K_WIDE
 EVAL_CHUNK, EVAL_MAX_CLASSES = 4096, 8                                                             # P2W_EVAL_*
 LOSS_CHUNK = 4096                                                                                  # P2W_LOSS_CHUNK
+EDGE_CHUNK = 1024                                                                                  # P2W_EDGE_CHUNK
 
 SIGNATURES = {
     "p2w_version": (_i32, []),
@@ -114,6 +115,9 @@ SIGNATURES = {
     "p2w_segment_max_bwd": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp]),
     "p2w_interp_bwd_ws_bytes": (_sz, [_i32, _i32, _i32]),
     "p2w_interp_bwd": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _sz, _vp]),
+    "p2w_edge_l1": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
+    "p2w_edge_l1_bwd_ws_bytes": (_sz, [_i32, _i32, _i32]),
+    "p2w_edge_l1_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -7,27 +7,9 @@
 // slot order after a stable sort, in a tree whose shape depends only on the sizes.
 // All kernels are bandwidth-bound: one wave covers 256 consecutive columns of a row with 16-byte accesses where rows and pointers
 // allow it (V = 4), and falls back to 4-byte accesses (V = 1, still coalesced) for odd widths.
-#include "p2w_common.h"
+#include "p2w_runsum.h"
 
 namespace {
-
-template <int V> __device__ __forceinline__ void gr_ld(const float* p, float (&v)[V]) {
-    if constexpr (V == 4) { const float4 t = *reinterpret_cast<const float4*>(p); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-    else v[0] = *p;
-}
-template <int V> __device__ __forceinline__ void gr_ld(const int* p, int (&v)[V]) {
-    if constexpr (V == 4) { const int4 t = *reinterpret_cast<const int4*>(p); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-    else v[0] = *p;
-}
-template <int V> __device__ __forceinline__ void gr_st(float* p, const float (&v)[V]) {
-    if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    else *p = v[0];
-}
-template <int V> __device__ __forceinline__ void gr_st(int* p, const int (&v)[V]) {
-    if constexpr (V == 4) *reinterpret_cast<int4*>(p) = make_int4(v[0], v[1], v[2], v[3]);
-    else *p = v[0];
-}
-inline bool gr_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // the order-preserving key of p2w_segment_max (p2w_feat.hip) and its inverse
 __device__ __forceinline__ unsigned gr_f2ord(float f) {
@@ -162,10 +144,6 @@ __global__ __launch_bounds__(256) void segmax_bwd_kernel(const float* __restrict
 // ------------------------------------------------------------------------------------------------ interpolation backward
 // one thread per fine row: the forward's weights (p2w_interp_concat / p2w_interp_weights: w = 1 / max(d2, 1e-16), a = w / sum w,
 // the sum in slot order) and the sort keys of the row's kw slots - the coarse index, n_coarse for a slot that is not in use
-constexpr int IB_PANEL = 256;        // columns per block pass: one wave of 16-byte lanes
-constexpr int IB_SPLIT_MIN = 512;    // mean run length from which the runs are split over blocks
-constexpr int IB_SPLIT_LEN = 256;    // ... into pieces of about this many slots
-constexpr int IB_SPLIT_MAX = 64;
 __global__ __launch_bounds__(256) void interp_bwd_prep_kernel(const float4* __restrict__ xyzr_c, const float4* __restrict__ xyzr_f,
                                                               const int* __restrict__ nbr, const int* __restrict__ deg, int kw, int m,
                                                               int n_coarse, unsigned long long* __restrict__ keys,
@@ -194,69 +172,30 @@ __global__ __launch_bounds__(256) void interp_bwd_prep_kernel(const float4* __re
     }
 }
 
-// One block per (coarse row j, piece z of its run, 256-column panel).  The run [start[j], start[j + 1]) of the sorted slot list is
-// cut into gridDim.y = Z pieces at L z / Z; inside a piece the block's P = 256 / W row lanes (W = 16-byte lanes per row, a power
-// of two <= 64) take slots p, p + P, ... in ascending order and are added in a binary tree in LDS.  Z, P and W follow from the
-// sizes alone, so the summation order of a row depends only on its run length.  Z == 1 writes grad_x, Z > 1 a partial row.
-__global__ __launch_bounds__(256) void interp_bwd_sum_kernel(const float* __restrict__ grad_out, int ldg, int F, const int* __restrict__ start,
-                                                             const int* __restrict__ slot, const float* __restrict__ wgt, int kw,
-                                                             int W, int c0, float* __restrict__ dst, int ldd, int dst_c0) {
-    __shared__ float4 sm[256];
-    const int j = blockIdx.x, z = blockIdx.y, Z = gridDim.y;
-    const int cl = threadIdx.x & (W - 1), p = threadIdx.x / W, P = 256 / W;
-    const int c = c0 + blockIdx.z * IB_PANEL + cl * 4;
-    const int s0 = start[j], L = start[j + 1] - s0;
-    const int a0 = s0 + (int)((long long)L * z / Z), a1 = s0 + (int)((long long)L * (z + 1) / Z);
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c < F) {
-#pragma unroll 4
-        for (int i = a0 + p; i < a1; i += P) {
-            const int sl = slot[i];
-            const float a = wgt[sl];
-            const float4 g = *reinterpret_cast<const float4*>(&grad_out[(size_t)(sl / kw) * ldg + c]);
-            acc.x = acc.x + a * g.x; acc.y = acc.y + a * g.y; acc.z = acc.z + a * g.z; acc.w = acc.w + a * g.w;
-        }
+// a slot's term of the run sums (p2w_runsum.h): its forward weight times the fine row's gradient
+struct InterpTerm {
+    const float* grad_out; int ldg; const float* wgt; int kw;
+    __device__ __forceinline__ void operator()(int sl, int c, float (&t)[4]) const {
+        const float a = wgt[sl];
+        float g[4];
+        gr_ld<4>(&grad_out[(size_t)(sl / kw) * ldg + c], g);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) t[u] = a * g[u];
     }
-    for (int h = P >> 1; h >= 1; h >>= 1) {
-        sm[threadIdx.x] = acc;
-        __syncthreads();
-        if (p < h) {
-            const float4 t = sm[threadIdx.x + h * W];
-            acc.x = acc.x + t.x; acc.y = acc.y + t.y; acc.z = acc.z + t.z; acc.w = acc.w + t.w;
-        }
-        __syncthreads();
-    }
-    if (p == 0 && c < F)
-        *reinterpret_cast<float4*>(&dst[((size_t)z * gridDim.x + j) * ldd + dst_c0 + blockIdx.z * IB_PANEL + cl * 4]) = acc;
-}
-// the Z partial rows of a panel, added in ascending z
-__global__ __launch_bounds__(256) void interp_bwd_combine_kernel(const float* __restrict__ part, int Z, int n_coarse, int F, int c0,
-                                                                 float* __restrict__ grad_x, int ldx) {
-    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int j = (int)(g >> 6), c = c0 + (int)(g & 63) * 4;
-    if (j >= n_coarse || c >= F) return;
-    float4 acc = *reinterpret_cast<const float4*>(&part[(size_t)j * IB_PANEL + (c - c0)]);
-    for (int z = 1; z < Z; ++z) {
-        const float4 t = *reinterpret_cast<const float4*>(&part[((size_t)z * n_coarse + j) * IB_PANEL + (c - c0)]);
-        acc.x = acc.x + t.x; acc.y = acc.y + t.y; acc.z = acc.z + t.z; acc.w = acc.w + t.w;
-    }
-    *reinterpret_cast<float4*>(&grad_x[(size_t)j * ldx + c]) = acc;
-}
+};
 
 inline size_t ib_up(size_t b) { return (b + 255) & ~size_t(255); }
 struct IbLayout { size_t keys_in, keys_out, slot, wgt, start, part, sub, sub_bytes, bytes; int Z; };
 inline void ib_layout(long long N, int n_coarse, IbLayout* L) {
     const size_t n1 = (size_t)(N > 0 ? N : 1);
-    const long long avg = n_coarse > 0 ? N / n_coarse : 0;
-    long long Z = avg >= IB_SPLIT_MIN ? avg / IB_SPLIT_LEN : 1;
-    L->Z = (int)(Z > IB_SPLIT_MAX ? IB_SPLIT_MAX : Z);
+    L->Z = run_pieces(N, n_coarse);
     size_t o = 0;
     L->keys_in = o;  o += ib_up(8 * n1);
     L->keys_out = o; o += ib_up(8 * n1);
     L->slot = o;     o += ib_up(4 * n1);
     L->wgt = o;      o += ib_up(4 * n1);
     L->start = o;    o += ib_up(4 * ((size_t)n_coarse + 1));
-    L->part = o;     o += L->Z > 1 ? ib_up((size_t)L->Z * n_coarse * IB_PANEL * sizeof(float)) : 0;      // Z n_coarse <= N / 256
+    L->part = o;     o += ib_up(run_part_bytes(L->Z, n_coarse, run_panel<4>()));
     const size_t a = p2w_sort_pairs_u64_ws_bytes((int32_t)n1), b = p2w_cell_starts_ws_bytes(n_coarse);
     L->sub = o; L->sub_bytes = ib_up(a > b ? a : b); o += L->sub_bytes;
     L->bytes = o;
@@ -340,18 +279,6 @@ extern "C" int32_t p2w_interp_bwd(const float* grad_out, int32_t ldg, int32_t F,
     }
     st = p2w_cell_starts(reinterpret_cast<const uint64_t*>(keys_out), N, n_coarse, start, w + L.sub, L.sub_bytes, stream);
     if (st != P2W_OK) return st;
-    const int q4 = F >> 2;
-    int W = 1;
-    while (W < q4 && W < 64) W <<= 1;
-    const int panels = p2w_cdiv(F, IB_PANEL);
-    if (L.Z == 1) {
-        interp_bwd_sum_kernel<<<dim3(n_coarse, 1, panels), 256, 0, s>>>(grad_out, ldg, F, start, slot, wgt, kw, W, 0, grad_x, ldx, 0);
-    } else {
-        for (int pnl = 0; pnl < panels; ++pnl) {
-            const int c0 = pnl * IB_PANEL;
-            interp_bwd_sum_kernel<<<dim3(n_coarse, L.Z, 1), 256, 0, s>>>(grad_out, ldg, F, start, slot, wgt, kw, W, c0, part, IB_PANEL, 0);
-            interp_bwd_combine_kernel<<<p2w_cdiv((long)n_coarse * 64, 256), 256, 0, s>>>(part, L.Z, n_coarse, F, c0, grad_x, ldx);
-        }
-    }
+    run_sum<4>(InterpTerm{grad_out, ldg, wgt, kw}, F, start, slot, n_coarse, L.Z, part, grad_x, ldx, s);
     return P2W_LAUNCH_STATUS();
 }

@@ -19,8 +19,9 @@ fuses the message/aggregate step); they exist for operator-level drop-in use and
 
 Gradients: ``global_max_pool``, ``scatter_max`` (and with it ``MessagePassing.propagate``) and ``knn_interpolate`` are
 differentiable with respect to their features (HIP backward kernels, ``csrc/p2w_grad.hip``, the same bits on every run);
-positions, batch vectors and indices get none.  A tied maximum sends its whole gradient to the lowest row.  The fused
-``PointNetConv`` and ``Net.forward`` stay inference-only.
+positions, batch vectors and indices get none.  A tied maximum sends its whole gradient to the lowest row.  ``PointNetConv``
+trains through ``edge_layer1`` (``csrc/p2w_edge.hip``: the hoisted layer 1 of the edge MLP with a deterministic backward) and
+``scatter_max``; its fused eval-mode kernel and ``Net.forward`` stay inference-only.
 """
 from __future__ import annotations
 
@@ -249,6 +250,81 @@ def knn_interpolate(x, pos_x, pos_y, batch_x=None, batch_y=None, k=3, num_worker
     return _interp_forward(x, rc, rf, nbr, deg, k)
 
 
+def _edge_l1_forward(P, Wg, rs, rd, csr, src):
+    """(geo [E, 4], H1 [E, C1]) of ``p2w_edge_l1``: fp32, contiguous inputs."""
+    (n_src, C1), M, E = P.shape, rd.shape[0], src.numel()
+    geo = torch.empty((E, 4), dtype=torch.float32, device=P.device)
+    H1 = torch.empty((E, C1), dtype=torch.float32, device=P.device)
+    check(lib().p2w_edge_l1(ptr(P), C1, ptr(rs), ptr(rd), ptr(csr), ptr(src), ptr(Wg), n_src, M, E, C1, ptr(geo), ptr(H1), C1,
+                            stream()), "edge_layer1")
+    return geo, H1
+
+
+def _f32c(t):
+    return _lib.aligned16(t.detach().to(torch.float32).contiguous())
+
+
+class _EdgeLayer1(torch.autograd.Function):
+    """``p2w_edge_l1`` forward, ``p2w_edge_l1_bwd`` backward: gradients with respect to P, Wg and column 3 of ``pos_src``.
+    H1 (the ReLU mask) and geo are saved for backward only."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, P, Wg, pos_src, rd, csr, src):
+        Pc, Wc = _f32c(P), _f32c(Wg)
+        geo, H1 = _edge_l1_forward(Pc, Wc, _f32c(pos_src), rd, csr, src)
+        ctx.save_for_backward(H1, geo, src, Wc)
+        ctx.n_src, ctx.dtypes = P.shape[0], (P.dtype, Wg.dtype, pos_src.dtype)
+        ctx.mark_non_differentiable(geo)
+        return H1, geo
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_H1, _grad_geo):
+        H1, geo, src, Wg = ctx.saved_tensors
+        (E, C1), n_src, dev = H1.shape, ctx.n_src, H1.device
+        g = _f32c(grad_H1)
+        gP = torch.empty((n_src, C1), dtype=torch.float32, device=dev)
+        gR = torch.empty(n_src, dtype=torch.float32, device=dev)
+        gWg = torch.empty((4, C1), dtype=torch.float32, device=dev)
+        need = int(lib().p2w_edge_l1_bwd_ws_bytes(E, n_src, C1))
+        if need == 0:
+            raise RuntimeError("p2w_edge_l1_bwd_ws_bytes failed")
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        check(lib().p2w_edge_l1_bwd(ptr(g), C1, ptr(H1), C1, ptr(geo), ptr(src), ptr(Wg), n_src, E, C1, ptr(gP), C1, ptr(gR), ptr(gWg),
+                                    ptr(ws), ws.numel(), stream()), "edge_layer1 backward")
+        gpos = None
+        if ctx.needs_input_grad[2]:
+            gpos = torch.zeros((n_src, 4), dtype=torch.float32, device=dev)
+            gpos[:, 3] = gR
+            gpos = gpos.to(ctx.dtypes[2])
+        return gP.to(ctx.dtypes[0]), gWg.to(ctx.dtypes[1]), gpos, None, None, None
+
+
+def edge_layer1(P, Wg, pos_src, pos_dst, edge_index):
+    """Layer 1 of the reference's edge MLP (``pointnet.py:116-132`` followed by ``local_nn[0]``, ``model.py:198-202``), hoisted:
+    ``H1[e] = relu(P[j] + geo[e] @ Wg)`` for edge e = (j -> i) with ``P = x_src @ W1[:, :F_in].T + b1`` ``[n_src, C1]`` computed by
+    the caller once per source point, ``Wg`` ``[4, C1]`` = the transposed last four columns of ``W1`` and ``geo[e] = ((pos_j - pos_i)
+    / (maxd_i + 1e-8), refl_j)``.  ``pos_*`` = [n, 4] (xyz, reflectance); ``edge_index`` = (source j, target i), grouped by target,
+    any number of edges per target.  One HIP kernel; the [E, F_in + 4] message tensor is never formed.
+
+    Differentiable with respect to ``P``, ``Wg`` and ``pos_src[:, 3]`` (the other columns of ``pos_src`` get zeros, ``pos_dst``
+    none: positions get no gradient anywhere in this module).  The backward uses no floating-point atomics: the same bits on
+    every run.  Computes in fp32 under autocast.  Without a gradient to track nothing is saved."""
+    _lib.require_cuda(P, Wg, pos_src, pos_dst, edge_index)
+    if P.dim() != 2 or tuple(Wg.shape) != (4, P.shape[1]) or pos_src.shape != (P.shape[0], 4) or pos_dst.dim() != 2 or pos_dst.shape[1] != 4:
+        raise RuntimeError("edge_layer1: P [n_src, C1], Wg [4, C1], pos_src [n_src, 4], pos_dst [M, 4]")
+    j, i = edge_index[0].to(torch.int64), edge_index[1].to(torch.int64)
+    n_src, M = P.shape[0], pos_dst.shape[0]
+    if j.numel() and (bool((i[1:] < i[:-1]).any()) or int(i[0]) < 0 or int(i[-1]) >= M or int(j.min()) < 0 or int(j.max()) >= n_src):
+        raise RuntimeError("edge_layer1: edges must be grouped by target (ascending edge_index[1]) and index existing points")
+    csr = torch.searchsorted(i.contiguous(), torch.arange(M + 1, device=i.device, dtype=torch.int64)).to(torch.int32)
+    src, rd = j.to(torch.int32).contiguous(), _f32c(pos_dst)
+    if torch.is_grad_enabled() and (P.requires_grad or Wg.requires_grad or pos_src.requires_grad):
+        return _EdgeLayer1.apply(P, Wg, pos_src, rd, csr, src)[0]
+    return _edge_l1_forward(_f32c(P), _f32c(Wg), _f32c(pos_src), rd, csr, src)[1]
+
+
 # --------------------------------------------------------------------------- the 8th operator
 class MessagePassing(torch.nn.Module):
     """The part of PyG's ``MessagePassing`` the reference uses (``pointnet.py:19,71,108``): ``propagate(edge_index, **kw)``
@@ -307,9 +383,8 @@ def _local_nn_weights(local_nn):
     except (TypeError, IndexError) as e:
         raise NotImplementedError("the fused PointNetConv supports local_nn = MLP([F_in + 4, C1, C2]) as the reference builds it") from e
     if bn.training:
-        raise RuntimeError("pointstowood_amd.ops.PointNetConv is inference-only: call .eval().  The route that trains is "
-                           "the unfused one: the reference's own PointNetConv subclass over ops.MessagePassing "
-                           "(its scatter_max has a backward)")
+        raise RuntimeError("the fused PointNetConv kernel is inference-only (its BatchNorm is folded from the running statistics): "
+                           "call .eval() on the whole layer, or .train() on the whole layer for the route that trains")
     s = (bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps))
     t = bn.bias.double() - bn.running_mean.double() * s
     return lin1.weight, lin1.bias, lin2.weight, lin2.bias, s.float(), t.float()
@@ -317,9 +392,15 @@ def _local_nn_weights(local_nn):
 
 class PointNetConv(MessagePassing):
     """Drop-in for the reference's ``src.pointnet.PointNetConv`` (``pointnet.py:19-132``; built at ``model.py:94``, called
-    at ``:123``) in eval mode: same constructor, same parameter names (``local_nn.*``), same
-    ``forward(x, (pos_src, pos_dst), edge_index)`` with ``pos`` = [n, 4] (sf-scaled xyz, reflectance) - message MLP +
-    max aggregation by ONE fused HIP kernel (``p2w_sa_conv``, fp32 MFMA: the [E, C] edge tensors are never formed) after a
+    at ``:123``): same constructor, same parameter names (``local_nn.*``), same
+    ``forward(x, (pos_src, pos_dst), edge_index)`` with ``pos`` = [n, 4] (sf-scaled xyz, reflectance).
+
+    Training mode: ``P = F.linear(x_src, W1[:, :F_in], b1)`` once per source point, ``edge_layer1`` (HIP, deterministic backward),
+    the module's own ``local_nn[1]`` (Linear, ReLU, training-mode BatchNorm1d: the running statistics update as in the
+    reference), ``scatter_max`` (HIP), ``global_nn``.  Gradients reach ``x``, ``pos_src[:, 3]`` and every parameter; xyz gets none.
+    Any number of edges per target.
+
+    Eval mode (under ``no_grad``): message MLP + max aggregation by ONE fused HIP kernel (``p2w_sa_conv``, fp32 MFMA: the [E, C] edge tensors are never formed) after a
     hoisted layer-1 GEMM (``p2w_gemm``).  Edges must be grouped by target with at most ``P2W_MAX_K_CONV`` = 32 per target
     (``radius(max_num_neighbors=32)`` / ``knn(k=32)`` as the reference calls them); ``global_nn`` is applied afterwards as
     in the reference; ``add_self_loops`` must be False (the reference passes False)."""
@@ -330,8 +411,38 @@ class PointNetConv(MessagePassing):
         super().__init__(**kw)
         self.local_nn, self.global_nn, self.add_self_loops = local_nn, global_nn, add_self_loops
 
-    @torch.no_grad()
     def forward(self, x, pos, edge_index):
+        return self._forward_train(x, pos, edge_index) if self.training else self._forward_fused(x, pos, edge_index)
+
+    def _forward_train(self, x, pos, edge_index):
+        from torch.nn import BatchNorm1d, Linear, ReLU
+        if self.add_self_loops:
+            raise NotImplementedError("add_self_loops=True is not supported (the reference builds the layer with False)")
+        if x is None or (isinstance(x, (tuple, list)) and x[0] is None):
+            raise NotImplementedError("PointNetConv: x = None is not supported (the reference's layers all carry features)")
+        x_src = x[0] if isinstance(x, (tuple, list)) else x
+        pos_src, pos_dst = pos if isinstance(pos, (tuple, list)) else (pos, pos)
+        _lib.require_cuda(x_src, pos_src, pos_dst, edge_index)
+        nn = self.local_nn
+        try:
+            ok = (len(nn) == 2 and len(nn[0]) == 2 and len(nn[1]) == 3 and isinstance(nn[0][0], Linear) and isinstance(nn[0][1], ReLU)
+                  and isinstance(nn[1][0], Linear) and isinstance(nn[1][1], ReLU) and isinstance(nn[1][2], BatchNorm1d))
+        except TypeError:
+            ok = False
+        if not ok:
+            raise NotImplementedError("PointNetConv supports local_nn = MLP([F_in + 4, C1, C2]) as the reference builds it")
+        lin1, F_in = nn[0][0], x_src.shape[1]
+        if lin1.weight.shape[1] != F_in + 4 or pos_src.shape[1] != 4 or pos_dst.shape[1] != 4:
+            raise RuntimeError("PointNetConv: local_nn must take F_in + 4 inputs, pos must be [n, 4]")
+        P = torch.nn.functional.linear(x_src, lin1.weight[:, :F_in], lin1.bias)     # hoisted layer 1, once per source point
+        H1 = edge_layer1(P, lin1.weight[:, F_in:F_in + 4].t(), pos_src, pos_dst, edge_index)
+        out = scatter_max(nn[1](H1), edge_index[1], dim=0, dim_size=pos_dst.shape[0])[0]
+        if self.global_nn is not None:
+            out = self.global_nn(out)
+        return out
+
+    @torch.no_grad()
+    def _forward_fused(self, x, pos, edge_index):
         import ctypes as C
         if self.add_self_loops:
             raise NotImplementedError("add_self_loops=True is not supported (the reference builds the layer with False)")
