@@ -629,6 +629,49 @@ int32_t p2w_edge_l1_bwd(const float* gH, int32_t ldg, const float* H1, int32_t l
                         const float* Wg, int32_t n_src, int32_t E, int32_t C1, float* gP, int32_t ldgp, float* gR, float* gWg, void* ws,
                         size_t ws_bytes, p2w_stream_t stream);
 
+/* ---- ReLU, training-mode BatchNorm1d and the max over the targets' edges in one (pointstowood_amd/ops.py: relu_bn_max) ---- */
+/* The tail of local_nn[1] and the aggregation of the training route (model.py:198-202, pointnet.py:122) on the layer-2 pre-activation
+ * z[E, C2] (pitch ldz), grouped by target: ptr[M + 1] is the CSR over the targets (ptr[0] = 0, ptr[M] = E, any degree).  Per column
+ * BatchNorm is an affine map, non-decreasing for gamma >= 0 and non-increasing for gamma < 0, so the maximum of BN(relu(z)) over a
+ * target's rows is BN of the rows' maximum of relu(z), or of their minimum where gamma < 0.  With y = z > 0 ? z : 0 (a NaN counts as 0):
+ *   mean[c]   = (1 / E) sum_e y[e, c],   var[c] = max((1 / E) sum_e y[e, c]^2 - mean[c]^2, 0),   invstd[c] = 1 / sqrt(var[c] + eps)
+ *               sums and arithmetic in fp64, each result rounded to fp32 once (var is the biased batch variance)
+ *   ext[i, c] = max (gamma[c] >= 0) or min (gamma[c] < 0) of y[e, c] over ptr[i] <= e < ptr[i + 1];      0 for a target without rows
+ *   arg[i, c] = the lowest such row that holds ext[i, c] (the tie rule of p2w_segment_max_arg: a segment of ReLU zeros sends
+ *               everything to its first row);                                                            -1 for a target without rows
+ *   out[i, c] = ((ext[i, c] - mean[c]) * invstd[c]) * gamma[c] + beta[c]     (fp32 on the rounded mean and invstd, no fma);    0 likewise
+ *   running_mean[c] = (1 - momentum) running_mean[c] + momentum mean[c],
+ *   running_var[c]  = (1 - momentum) running_var[c]  + momentum var[c] E / (E - 1)          (in place, fp64 arithmetic, rounded once)
+ * out, ext, arg are dense [M, C2]; gamma, beta, running_*, mean, invstd [C2].  z is read once.  Three launches: the fp64 column sums
+ * and the extrema per work item of P2W_BN_GROUP consecutive targets (one lane per column walks the item's rows in ascending order);
+ * the items in ascending order, and the statistics; the map on [M, C2].  No floating-point atomics: the bits depend on the inputs
+ * alone, not on the run, the grid or the access width.
+ * The kernels clamp ptr to [0, E] and make it non-decreasing, so no offset is followed out of bounds; ptr[0] = 0 and ptr[M] = E are
+ * the caller's contract (they cannot be checked without a synchronisation: rows outside [ptr[0], ptr[M]) enter no sum).
+ * Access width: 16 bytes per lane when C2 and ldz are multiples of 4 and z, gamma, beta, out, ext, arg, mean, invstd are 16-byte
+ * aligned, 4 bytes otherwise (same bits).  ws: 16-byte aligned (P2W_EALIGN), p2w_relu_bn_max_ws_bytes(E, M, C2) bytes (0 = bad sizes;
+ * too small: P2W_EWORKSPACE).  2 <= E < 2^31 - 1 (one row has no variance), 1 <= M < 2^31 - 1, C2 >= 1, M C2 <= 2^38, ldz >= C2,
+ * eps >= 0, 0 <= momentum <= 1 (P2W_EINVAL); every pointer is required (P2W_ENULL).  Nothing is allocated, and a refused call
+ * launches nothing. */
+#define P2W_BN_GROUP 16
+size_t p2w_relu_bn_max_ws_bytes(int32_t E, int32_t M, int32_t C2);
+int32_t p2w_relu_bn_max(const float* z, int32_t ldz, const int32_t* ptr, const float* gamma, const float* beta, float* running_mean,
+                        float* running_var, double momentum, double eps, int32_t E, int32_t M, int32_t C2, float* out, float* ext,
+                        int32_t* arg, float* mean, float* invstd, void* ws, size_t ws_bytes, p2w_stream_t stream);
+/* Its backward, on what the forward left (arg, ext, mean, invstd) and the gradient g[M, C2] (dense) of out.  Over the targets with rows:
+ *   dbeta[c]  = sum_i g[i, c],      dgamma[c] = sum_i g[i, c] ((ext[i, c] - mean[c]) invstd[c])
+ *               fp64 terms on the fp32 inputs, fp64 partials per P2W_BN_GROUP consecutive targets in ascending order, the groups in
+ *               ascending order, rounded to fp32 once; k1 = dbeta / E and k2 = dgamma / E likewise
+ *   xhat      = (y[e, c] - mean[c]) * invstd[c]
+ *   dy[e, c]  = (((arg[i(e), c] == e ? g[i(e), c] : 0) - k1[c]) - xhat * k2[c]) * (gamma[c] * invstd[c])        (fp32, no fma)
+ *   dz[e, c]  = z[e, c] > 0 ? dy[e, c] : 0                                                                     (pitch lddz)
+ * z is read once and every element of dz's rows [ptr[0], ptr[M]) = [0, E) is written once; dgamma and dbeta [C2] are written, not added
+ * to.  Three launches; no floating-point atomics.  Access width as in the forward (g, z, arg, ext, mean, invstd, gamma, dz, ldz and
+ * lddz decide it); ws and sizes as in the forward, lddz >= C2. */
+int32_t p2w_relu_bn_max_bwd(const float* g, const float* z, int32_t ldz, const int32_t* ptr, const int32_t* arg, const float* ext,
+                            const float* mean, const float* invstd, const float* gamma, int32_t E, int32_t M, int32_t C2, float* dz,
+                            int32_t lddz, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, p2w_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

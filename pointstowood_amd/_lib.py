@@ -34,6 +34,7 @@ MAX_K_WIDE = 100                                                                
 EVAL_CHUNK, EVAL_MAX_CLASSES = 4096, 8                                                             # P2W_EVAL_*
 LOSS_CHUNK = 4096                                                                                  # P2W_LOSS_CHUNK
 EDGE_CHUNK = 1024                                                                                  # P2W_EDGE_CHUNK
+BN_GROUP = 16                                                                                      # P2W_BN_GROUP
 
 SIGNATURES = {
     "p2w_version": (_i32, []),
@@ -118,6 +119,10 @@ SIGNATURES = {
     "p2w_edge_l1": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "p2w_edge_l1_bwd_ws_bytes": (_sz, [_i32, _i32, _i32]),
     "p2w_edge_l1_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "p2w_relu_bn_max_ws_bytes": (_sz, [_i32, _i32, _i32]),
+    "p2w_relu_bn_max": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                               _vp]),
+    "p2w_relu_bn_max_bwd": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -21,7 +21,9 @@ Gradients: ``global_max_pool``, ``scatter_max`` (and with it ``MessagePassing.pr
 differentiable with respect to their features (HIP backward kernels, ``csrc/p2w_grad.hip``, the same bits on every run);
 positions, batch vectors and indices get none.  A tied maximum sends its whole gradient to the lowest row.  ``PointNetConv``
 trains through ``edge_layer1`` (``csrc/p2w_edge.hip``: the hoisted layer 1 of the edge MLP with a deterministic backward) and
-``scatter_max``; its fused eval-mode kernel and ``Net.forward`` stay inference-only.
+``scatter_max``, or, with ``fused_bn_max``, through ``relu_bn_max`` (``csrc/p2w_bnmax.hip``: ReLU, training-mode BatchNorm1d and the
+segment max in one forward and one backward kernel, differentiable with respect to its input and BatchNorm's weight and bias); its
+fused eval-mode kernel and ``Net.forward`` stay inference-only.
 """
 from __future__ import annotations
 
@@ -325,6 +327,106 @@ def edge_layer1(P, Wg, pos_src, pos_dst, edge_index):
     return _edge_l1_forward(_f32c(P), _f32c(Wg), _f32c(pos_src), rd, csr, src)[1]
 
 
+def _relu_bn_max_forward(zc, gamma, beta, csr, M, bn):
+    """(out, ext, arg, mean, invstd) of ``p2w_relu_bn_max`` on fp32, contiguous inputs; bn's running statistics move in place."""
+    (E, C2), dev = zc.shape, zc.device
+    out, ext = (torch.empty((M, C2), dtype=torch.float32, device=dev) for _ in range(2))
+    arg = torch.empty((M, C2), dtype=torch.int32, device=dev)
+    mean, invstd = (torch.empty(C2, dtype=torch.float32, device=dev) for _ in range(2))
+    rm, rv = (t.detach().to(torch.float32).contiguous() for t in (bn.running_mean, bn.running_var))
+    need = int(lib().p2w_relu_bn_max_ws_bytes(E, M, C2))
+    if need == 0:
+        raise RuntimeError("p2w_relu_bn_max_ws_bytes failed")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    check(lib().p2w_relu_bn_max(ptr(zc), C2, ptr(csr), ptr(gamma), ptr(beta), ptr(rm), ptr(rv), float(bn.momentum), float(bn.eps), E, M, C2,
+                                ptr(out), ptr(ext), ptr(arg), ptr(mean), ptr(invstd), ptr(ws), ws.numel(), stream()), "relu_bn_max")
+    with torch.no_grad():
+        for mine, theirs in ((rm, bn.running_mean), (rv, bn.running_var)):
+            if mine.data_ptr() != theirs.data_ptr():
+                theirs.copy_(mine)
+    return out, ext, arg, mean, invstd
+
+
+class _ReluBnMax(torch.autograd.Function):
+    """``p2w_relu_bn_max`` forward, ``p2w_relu_bn_max_bwd`` backward: gradients with respect to z, gamma and beta.  Saved for backward:
+    z, arg, ext, mean, invstd, the CSR and gamma - no [E, C2] tensor besides z itself."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, z, gamma, beta, csr, M, bn):
+        zc, gc = _f32c(z), _f32c(gamma)
+        out, ext, arg, mean, invstd = _relu_bn_max_forward(zc, gc, _f32c(beta), csr, M, bn)
+        ctx.save_for_backward(zc, arg, ext, mean, invstd, csr, gc)
+        ctx.dtypes = (z.dtype, gamma.dtype, beta.dtype)
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_out):
+        z, arg, ext, mean, invstd, csr, gamma = ctx.saved_tensors
+        (E, C2), M, dev = z.shape, arg.shape[0], z.device
+        g = _f32c(grad_out)
+        dz = torch.empty((E, C2), dtype=torch.float32, device=dev)
+        dgamma, dbeta = (torch.empty(C2, dtype=torch.float32, device=dev) for _ in range(2))
+        need = int(lib().p2w_relu_bn_max_ws_bytes(E, M, C2))
+        if need == 0:
+            raise RuntimeError("p2w_relu_bn_max_ws_bytes failed")
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        check(lib().p2w_relu_bn_max_bwd(ptr(g), ptr(z), C2, ptr(csr), ptr(arg), ptr(ext), ptr(mean), ptr(invstd), ptr(gamma), E, M, C2,
+                                        ptr(dz), C2, ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), stream()), "relu_bn_max backward")
+        return dz.to(ctx.dtypes[0]), dgamma.to(ctx.dtypes[1]), dbeta.to(ctx.dtypes[2]), None, None, None
+
+
+def _relu_bn_max_sorted(z, index, bn, M):
+    """``relu_bn_max`` on an index that is known to be ascending and inside [0, M)."""
+    if not bn.training:
+        return scatter_max(bn(torch.relu(z)), index, dim=0, dim_size=M)[0]
+    if z.shape[0] < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {z.size()}")
+    csr = torch.searchsorted(index.to(torch.int64).contiguous(), torch.arange(M + 1, device=index.device, dtype=torch.int64)).to(torch.int32)
+    if bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    if torch.is_grad_enabled() and (z.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad):
+        return _ReluBnMax.apply(z, bn.weight, bn.bias, csr, M, bn)
+    return _relu_bn_max_forward(_f32c(z), _f32c(bn.weight), _f32c(bn.bias), csr, M, bn)[0]
+
+
+def relu_bn_max(z, index, bn, dim_size=None):
+    """``scatter_max(bn(relu(z)), index, dim=0, dim_size=dim_size)[0]`` for a ``torch.nn.BatchNorm1d`` ``bn`` in training mode without
+    the three [E, C] tensors in between (the tail of the reference's edge MLP and its aggregation, ``model.py:198-202`` and
+    ``pointnet.py:122``): per column BatchNorm is an affine map, non-decreasing for ``gamma >= 0`` and non-increasing for ``gamma < 0``,
+    so the maximum of ``bn(relu(z))`` over a target's rows is bn of the rows' maximum of ``relu(z)`` (their minimum where ``gamma < 0``).
+    ``z`` [E, C] is the pre-activation, ``index`` [E] the ascending target of every row (as for ``scatter_max``), ``dim_size`` the
+    number of targets (default ``index.max() + 1``); targets without rows get 0.
+
+    Two HIP kernels (``csrc/p2w_bnmax.hip``): the forward reads ``z`` once (fp64 column sums of ``relu(z)`` and its square, one
+    extremum and its lowest row per target and column) and updates ``bn.running_mean``, ``bn.running_var`` (unbiased variance) and
+    ``bn.num_batches_tracked`` as PyTorch does; the backward reads ``z`` once more and writes the gradient with respect to ``z`` once,
+    BatchNorm's gradient through the batch statistics included.  Gradients go to ``z``, ``bn.weight`` and ``bn.bias`` in their dtypes;
+    a tied extremum sends its gradient to the lowest row (``scatter_max``'s rule).  Where ``gamma == 0`` the output does not depend on
+    the winner; the gradient with respect to gamma is taken on the ``gamma >= 0`` side (through the maximum).  No floating-point
+    atomics: the same bits on every run, the batch statistics included.  Saved for backward: ``z`` and [M, C] / [C] tensors only.
+    Computes in fp32 under autocast (a float16 ``z`` is cast first: one extra pass).  Under ``no_grad`` the forward runs, the running
+    statistics move, and nothing is saved.
+
+    With ``bn.training`` false this is the composition itself, ``scatter_max(bn(relu(z)))`` on the running statistics: the kernels'
+    backward carries the batch-statistics terms, so eval mode would need a second backward, not a flag.  ``affine=False``,
+    ``track_running_stats=False`` and ``momentum=None`` raise ``NotImplementedError`` (the reference builds none of them); fewer than
+    two rows in training mode raise PyTorch's ``ValueError``."""
+    _lib.require_cuda(z, index)
+    if not isinstance(bn, torch.nn.BatchNorm1d):
+        raise TypeError("relu_bn_max: bn must be a torch.nn.BatchNorm1d")
+    if not bn.affine or not bn.track_running_stats or bn.momentum is None:
+        raise NotImplementedError("relu_bn_max supports BatchNorm1d(affine=True, track_running_stats=True, momentum=<float>) as the reference builds it")
+    if z.dim() != 2 or z.shape[1] != bn.num_features or index.dim() != 1 or index.numel() != z.shape[0]:
+        raise RuntimeError("relu_bn_max: z [E, C] with C = bn.num_features, index [E]")
+    i = index.to(torch.int64)
+    M = (int(i.max()) + 1 if i.numel() else 1) if dim_size is None else int(dim_size)
+    if i.numel() and (bool((i[1:] < i[:-1]).any()) or int(i[0]) < 0 or int(i[-1]) >= M):
+        raise RuntimeError("relu_bn_max: index must be ascending and inside [0, dim_size)")
+    return _relu_bn_max_sorted(z, i, bn, M)
+
+
 # --------------------------------------------------------------------------- the 8th operator
 class MessagePassing(torch.nn.Module):
     """The part of PyG's ``MessagePassing`` the reference uses (``pointnet.py:19,71,108``): ``propagate(edge_index, **kw)``
@@ -403,7 +505,14 @@ class PointNetConv(MessagePassing):
     Eval mode (under ``no_grad``): message MLP + max aggregation by ONE fused HIP kernel (``p2w_sa_conv``, fp32 MFMA: the [E, C] edge tensors are never formed) after a
     hoisted layer-1 GEMM (``p2w_gemm``).  Edges must be grouped by target with at most ``P2W_MAX_K_CONV`` = 32 per target
     (``radius(max_num_neighbors=32)`` / ``knn(k=32)`` as the reference calls them); ``global_nn`` is applied afterwards as
-    in the reference; ``add_self_loops`` must be False (the reference passes False)."""
+    in the reference; ``add_self_loops`` must be False (the reference passes False).
+
+    ``fused_bn_max`` (default False; set it on the instance or the class): the training route computes everything after the layer-2
+    GEMM with ``relu_bn_max`` instead of ReLU, BatchNorm1d and ``scatter_max`` one after the other - no [E, C2] tensor besides the
+    GEMM's output, the same bits on every run.  False leaves every launch and bit of the training route as it was; eval mode does
+    not look at it."""
+
+    fused_bn_max = False
 
     def __init__(self, local_nn=None, global_nn=None, add_self_loops=True, **kw):
         self.radius = kw.pop("radius", None)
@@ -436,7 +545,10 @@ class PointNetConv(MessagePassing):
             raise RuntimeError("PointNetConv: local_nn must take F_in + 4 inputs, pos must be [n, 4]")
         P = torch.nn.functional.linear(x_src, lin1.weight[:, :F_in], lin1.bias)     # hoisted layer 1, once per source point
         H1 = edge_layer1(P, lin1.weight[:, F_in:F_in + 4].t(), pos_src, pos_dst, edge_index)
-        out = scatter_max(nn[1](H1), edge_index[1], dim=0, dim_size=pos_dst.shape[0])[0]
+        if self.fused_bn_max:       # (edge_layer1 has checked that the targets ascend inside [0, M))
+            out = _relu_bn_max_sorted(nn[1][0](H1), edge_index[1], nn[1][2], pos_dst.shape[0])
+        else:
+            out = scatter_max(nn[1](H1), edge_index[1], dim=0, dim_size=pos_dst.shape[0])[0]
         if self.global_nn is not None:
             out = self.global_nn(out)
         return out
