@@ -283,8 +283,14 @@ int32_t p2w_knn_wide_f64(const double* xyz_sorted, const int32_t* order, const u
  * iteration) as the reference takes them; where no remaining row holds a processed point the growth stops (the reference raises its
  * threshold for ever there) and the rest stays -1.  Out: step_out[n] = the step at which each point was processed (base 0, -1 never);
  * edges_out[edge_cap][2] = the edges (g, e) in no particular order, duplicates and self-loops included; info_out (HOST, 6 int64) =
- * {edges, step at which the loop stopped, gap steps, threshold raises, launches, 1 if points were left unreached}; threshold_out (HOST)
- * = the final nbrs_threshold.  edge_cap >= n * 3 * (min(kpairs + 1, k)) always suffices (P2W_EWORKSPACE when the edges overflow).
+ * {edges, stop step, gap steps, threshold raises, launches, 1 if points were left unreached}; threshold_out (HOST) = the final
+ * nbrs_threshold.  Stop step = the last step that had a non-empty frontier or raised the threshold.  The reference's loop ends right
+ * after the step S that processed the last point; here the frontier step S + 1 still runs (it finds every row entry processed and
+ * adds nothing) and the empty frontier of S + 2 ends the growth, so with every point processed the stop step is max(step_out) + 1 =
+ * the reference's final current_step + 1 - and equal to it, 1, for n = 1, where the reference's only step is that empty-handed one.
+ * With points left unreached it is the step BEFORE the one that found so (the first empty frontier with no remaining row holding a
+ * processed point: max(step_out) + 1 again; or the step whose fp64 threshold addition changed nothing: the last raise).
+ * edge_cap >= n * 3 * (min(kpairs + 1, k)) always suffices (P2W_EWORKSPACE when the edges overflow).
  * Blocks the host (the state is read back between launch batches and at every empty frontier).  nbrs_threshold_step finite and > 0.
  * ws: 16-byte aligned, p2w_pathlen_grow_ws_bytes(n) bytes. */
 size_t p2w_pathlen_grow_ws_bytes(int64_t n);

@@ -107,12 +107,14 @@ __global__ __launch_bounds__(PL_THREADS) void pl_knn_kernel(const double* __rest
 #pragma unroll 1
     for (long long s = 0;; ++s) {
         // ring s: the cells whose largest per-axis offset from (cx, cy, cz) is s, as runs of one grid row each
-        for (long long dz = -s; dz <= s; ++dz) {
+        // (the offsets are clipped to the grid before the loops: a cloud on a line or in a plane has a grid one cell thick, and its
+        // searches run to hundreds of rings - walking the (2 s + 1)^2 rows outside it cost 11 s on 400 collinear points at k = 65)
+        const long long za = cz - s < 0 ? -cz : -s, zb = cz + s >= d2 ? d2 - 1 - cz : s;
+        const long long ya = cy - s < 0 ? -cy : -s, yb = cy + s >= d1 ? d1 - 1 - cy : s;
+        for (long long dz = za; dz <= zb; ++dz) {
             const long long z = cz + dz;
-            if (z < 0 || z >= d2) continue;
-            for (long long dy = -s; dy <= s; ++dy) {
+            for (long long dy = ya; dy <= yb; ++dy) {
                 const long long y = cy + dy;
-                if (y < 0 || y >= d1) continue;
                 const long long row = (z * d1 + y) * d0;
                 if (dz == -s || dz == s || dy == -s || dy == s) {
                     const long long xa = cx - s < 0 ? 0 : cx - s, xb = cx + s >= d0 ? d0 - 1 : cx + s;
@@ -538,7 +540,7 @@ extern "C" int32_t p2w_pathlen_grow(const double* xyz, const int32_t* nbr, int64
     if ((e = pl_read_state(st, h, s)) != hipSuccess) return (int32_t)e;
     if (h[ST_OVERFLOW]) return P2W_EWORKSPACE;
     info_out[0] = (int64_t)h[ST_EDGES];
-    info_out[1] = t;                                                      // the step at which the growth loop stopped
+    info_out[1] = t;                                                      // the last step with a frontier or a raise (p2w.h)
     info_out[2] = gaps;
     info_out[3] = raises;
     info_out[4] = launches;
