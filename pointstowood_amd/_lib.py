@@ -154,6 +154,14 @@ def check(code: int, what: str = "") -> None:
         raise RuntimeError(f"{what or 'p2w'} failed: {msg} (code {code})")
 
 
+def ws_bytes(name: str, *args) -> int:
+    """Workspace size of entry point ``name`` (``p2w_<name>_ws_bytes``); 0 is the library's answer to sizes it refuses."""
+    need = int(getattr(lib(), f"p2w_{name}_ws_bytes")(*args))
+    if need == 0:
+        raise RuntimeError(f"p2w_{name}_ws_bytes{args} failed")
+    return need
+
+
 def ptr(t):
     """Raw device pointer of a tensor (None -> NULL)."""
     return None if t is None else t.data_ptr()

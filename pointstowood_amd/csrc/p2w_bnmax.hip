@@ -237,14 +237,13 @@ __global__ __launch_bounds__(256) void bnmax_dz_kernel(const float* __restrict__
     }
 }
 
-inline size_t bm_up(size_t b) { return (b + 255) & ~size_t(255); }
-struct BmLayout { size_t part, kq, bytes; int items; };
-inline void bm_layout(int M, int C2, BmLayout* L) {
-    L->items = p2w_cdiv(M, BN_G);
-    size_t o = 0;
-    L->part = o; o += bm_up((size_t)L->items * 2 * C2 * sizeof(double));
-    L->kq = o;   o += bm_up((size_t)2 * C2 * sizeof(float));
-    L->bytes = o;
+struct BmWs { double* part; float* kq; int items; };
+inline BmWs bm_carve(P2wArena& a, int M, int C2) {
+    BmWs W;
+    W.items = p2w_cdiv(M, BN_G);
+    W.part = a.take<double>((size_t)W.items * 2 * C2);
+    W.kq = a.take<float>((size_t)2 * C2);
+    return W;
 }
 inline bool bm_sizes_ok(long long E, long long M, long long C2) {
     return E >= 2 && M >= 1 && C2 >= 1 && E < 0x7fffffffll && M < 0x7fffffffll && M * C2 <= (1ll << 38);     // (grids of M C2 / 4 / 256 blocks)
@@ -254,9 +253,7 @@ inline bool bm_sizes_ok(long long E, long long M, long long C2) {
 
 extern "C" size_t p2w_relu_bn_max_ws_bytes(int32_t E, int32_t M, int32_t C2) {
     if (!bm_sizes_ok(E, M, C2)) return 0;
-    BmLayout L;
-    bm_layout(M, C2, &L);
-    return L.bytes;
+    return p2w_ws_bytes([&](P2wArena& a) { bm_carve(a, M, C2); });
 }
 
 extern "C" int32_t p2w_relu_bn_max(const float* z, int32_t ldz, const int32_t* ptr, const float* gamma, const float* beta,
@@ -267,18 +264,17 @@ extern "C" int32_t p2w_relu_bn_max(const float* z, int32_t ldz, const int32_t* p
     P2W_CHECK_PTR(z); P2W_CHECK_PTR(ptr); P2W_CHECK_PTR(gamma); P2W_CHECK_PTR(beta); P2W_CHECK_PTR(running_mean); P2W_CHECK_PTR(running_var);
     P2W_CHECK_PTR(out); P2W_CHECK_PTR(ext); P2W_CHECK_PTR(arg); P2W_CHECK_PTR(mean); P2W_CHECK_PTR(invstd); P2W_CHECK_PTR(ws);
     P2W_CHECK_ALIGN16(ws);
-    BmLayout L;
-    bm_layout(M, C2, &L);
-    if (ws_bytes < L.bytes) return P2W_EWORKSPACE;
+    P2wArena arena(ws);
+    const BmWs L = bm_carve(arena, M, C2);
+    if (ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
     const bool v4 = !(C2 & 3) && !(ldz & 3) && gr_al16(z) && gr_al16(gamma) && gr_al16(beta) && gr_al16(out) && gr_al16(ext) && gr_al16(arg) &&
                     gr_al16(mean) && gr_al16(invstd);
     hipStream_t s = p2w_s(stream);
-    double* part = reinterpret_cast<double*>(static_cast<char*>(ws) + L.part);
     const int q = v4 ? C2 >> 2 : C2;
     const unsigned pb = (unsigned)(((long long)L.items * q + 255) / 256), ab = (unsigned)(((long long)M * q + 255) / 256);
-    if (v4) bnmax_part_kernel<4><<<pb, 256, 0, s>>>(z, ldz, ptr, gamma, M, E, C2, q, L.items, ext, arg, part);
-    else bnmax_part_kernel<1><<<pb, 256, 0, s>>>(z, ldz, ptr, gamma, M, E, C2, q, L.items, ext, arg, part);
-    bnmax_reduce_kernel<<<p2w_cdiv(C2, RED_COLS), 256, 0, s>>>(part, L.items, C2, E, true, momentum, eps, mean, invstd, running_mean,
+    if (v4) bnmax_part_kernel<4><<<pb, 256, 0, s>>>(z, ldz, ptr, gamma, M, E, C2, q, L.items, ext, arg, L.part);
+    else bnmax_part_kernel<1><<<pb, 256, 0, s>>>(z, ldz, ptr, gamma, M, E, C2, q, L.items, ext, arg, L.part);
+    bnmax_reduce_kernel<<<p2w_cdiv(C2, RED_COLS), 256, 0, s>>>(L.part, L.items, C2, E, true, momentum, eps, mean, invstd, running_mean,
                                                                running_var, nullptr);
     if (v4) bnmax_apply_kernel<4><<<ab, 256, 0, s>>>(ext, arg, mean, invstd, gamma, beta, M, C2, q, out);
     else bnmax_apply_kernel<1><<<ab, 256, 0, s>>>(ext, arg, mean, invstd, gamma, beta, M, C2, q, out);
@@ -292,20 +288,18 @@ extern "C" int32_t p2w_relu_bn_max_bwd(const float* g, const float* z, int32_t l
     P2W_CHECK_PTR(g); P2W_CHECK_PTR(z); P2W_CHECK_PTR(ptr); P2W_CHECK_PTR(arg); P2W_CHECK_PTR(ext); P2W_CHECK_PTR(mean); P2W_CHECK_PTR(invstd);
     P2W_CHECK_PTR(gamma); P2W_CHECK_PTR(dz); P2W_CHECK_PTR(dgamma); P2W_CHECK_PTR(dbeta); P2W_CHECK_PTR(ws);
     P2W_CHECK_ALIGN16(ws);
-    BmLayout L;
-    bm_layout(M, C2, &L);
-    if (ws_bytes < L.bytes) return P2W_EWORKSPACE;
+    P2wArena arena(ws);
+    const BmWs L = bm_carve(arena, M, C2);
+    if (ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
     const bool v4 = !(C2 & 3) && !(ldz & 3) && !(lddz & 3) && gr_al16(g) && gr_al16(z) && gr_al16(arg) && gr_al16(ext) && gr_al16(mean) &&
                     gr_al16(invstd) && gr_al16(gamma) && gr_al16(dz);
     hipStream_t s = p2w_s(stream);
-    double* part = reinterpret_cast<double*>(static_cast<char*>(ws) + L.part);
-    float* kq = reinterpret_cast<float*>(static_cast<char*>(ws) + L.kq);
     const int q = v4 ? C2 >> 2 : C2;
     const unsigned pb = (unsigned)(((long long)L.items * q + 255) / 256);
-    if (v4) bnmax_bwd_part_kernel<4><<<pb, 256, 0, s>>>(g, ext, arg, mean, invstd, M, C2, q, L.items, part);
-    else bnmax_bwd_part_kernel<1><<<pb, 256, 0, s>>>(g, ext, arg, mean, invstd, M, C2, q, L.items, part);
-    bnmax_reduce_kernel<<<p2w_cdiv(C2, RED_COLS), 256, 0, s>>>(part, L.items, C2, E, false, 0.0, 0.0, dgamma, dbeta, nullptr, nullptr, kq);
-    if (v4) bnmax_dz_kernel<4><<<L.items, 256, 0, s>>>(g, z, ldz, ptr, arg, mean, invstd, gamma, kq, M, E, C2, run_row_lanes<4>(C2), dz, lddz);
-    else bnmax_dz_kernel<1><<<L.items, 256, 0, s>>>(g, z, ldz, ptr, arg, mean, invstd, gamma, kq, M, E, C2, run_row_lanes<1>(C2), dz, lddz);
+    if (v4) bnmax_bwd_part_kernel<4><<<pb, 256, 0, s>>>(g, ext, arg, mean, invstd, M, C2, q, L.items, L.part);
+    else bnmax_bwd_part_kernel<1><<<pb, 256, 0, s>>>(g, ext, arg, mean, invstd, M, C2, q, L.items, L.part);
+    bnmax_reduce_kernel<<<p2w_cdiv(C2, RED_COLS), 256, 0, s>>>(L.part, L.items, C2, E, false, 0.0, 0.0, dgamma, dbeta, nullptr, nullptr, L.kq);
+    if (v4) bnmax_dz_kernel<4><<<L.items, 256, 0, s>>>(g, z, ldz, ptr, arg, mean, invstd, gamma, L.kq, M, E, C2, run_row_lanes<4>(C2), dz, lddz);
+    else bnmax_dz_kernel<1><<<L.items, 256, 0, s>>>(g, z, ldz, ptr, arg, mean, invstd, gamma, L.kq, M, E, C2, run_row_lanes<1>(C2), dz, lddz);
     return P2W_LAUNCH_STATUS();
 }

@@ -143,24 +143,22 @@ __global__ __launch_bounds__(256) void ec_label_kernel(const int* __restrict__ r
     if (i == n - 1) counts[0] = cid[i] + ((root[i] == i && ec_kept(size[i], min_size, max_size)) ? 1 : 0);
 }
 
-struct EcLayout { size_t parent, root, size, keep, temp, total; };
+struct EcWs { int *parent, *root, *size, *keep; void* temp; };
 
-EcLayout ec_layout(long long n) {
-    auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
-    const size_t words = up(sizeof(int) * (size_t)(n > 0 ? n : 1));
-    EcLayout L;
-    L.parent = 0;
-    L.root = L.parent + words;
-    L.size = L.root + words;
-    L.keep = L.size + words;
-    L.temp = L.keep + words;
-    L.total = L.temp + up(xs_ws_bytes(n));
-    return L;
+EcWs ec_carve(P2wArena& a, long long n) {
+    const size_t words = (size_t)(n > 0 ? n : 1);
+    EcWs W;
+    W.parent = a.take<int>(words);
+    W.root = a.take<int>(words);
+    W.size = a.take<int>(words);
+    W.keep = a.take<int>(words);
+    W.temp = a.raw(xs_ws_bytes(n));
+    return W;
 }
 
 }  // namespace
 
-extern "C" size_t p2w_euclid_cluster_ws_bytes(int64_t n) { return ec_layout(n).total; }
+extern "C" size_t p2w_euclid_cluster_ws_bytes(int64_t n) { return p2w_ws_bytes([&](P2wArena& a) { ec_carve(a, n); }); }
 
 extern "C" int32_t p2w_euclid_cluster(const double* xyz_sorted, const int32_t* order, const uint64_t* keys_sorted, const int32_t* cell_start,
                                       const p2w_grid* grid, int64_t n, double tolerance, int64_t min_size, int64_t max_size,
@@ -170,17 +168,14 @@ extern "C" int32_t p2w_euclid_cluster(const double* xyz_sorted, const int32_t* o
     if (!(tolerance >= 0.0) || tolerance == HUGE_VAL) return P2W_EINVAL;             // NaN, negative or infinite
     if (stages <= 0 || (stages & ~P2W_CLUSTER_ALL) != 0) return P2W_EINVAL;
     P2W_CHECK_PTR(ws); P2W_CHECK_ALIGN16(ws);
-    const EcLayout L = ec_layout(n);
-    if (ws_bytes < L.total) return P2W_EWORKSPACE;
+    P2wArena arena(ws);
+    const EcWs L = ec_carve(arena, n);
+    if (ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
     if (stages & P2W_CLUSTER_LINK) { P2W_CHECK_PTR(xyz_sorted); P2W_CHECK_PTR(keys_sorted); P2W_CHECK_PTR(grid); }
     if (stages & (P2W_CLUSTER_LINK | P2W_CLUSTER_COMPRESS)) P2W_CHECK_PTR(order);
     if (stages & P2W_CLUSTER_NUMBER) { P2W_CHECK_PTR(labels_out); P2W_CHECK_PTR(counts_out); }
     hipStream_t s = p2w_s(stream);
-    char* w = static_cast<char*>(ws);
-    int* parent = reinterpret_cast<int*>(w + L.parent);
-    int* root = reinterpret_cast<int*>(w + L.root);
-    int* size = reinterpret_cast<int*>(w + L.size);
-    int* keep = reinterpret_cast<int*>(w + L.keep);
+    int *parent = L.parent, *root = L.root, *size = L.size, *keep = L.keep;
     const int nn = (int)n, nblk = p2w_cdiv(nn, 256);
     hipError_t e;
     if (stages & P2W_CLUSTER_LINK) {
@@ -197,7 +192,7 @@ extern "C" int32_t p2w_euclid_cluster(const double* xyz_sorted, const int32_t* o
         if ((e = hipMemsetAsync(counts_out, 0, 2 * sizeof(int32_t), s)) != hipSuccess) return (int32_t)e;
         if (nn > 0) {
             ec_keep_kernel<<<nblk, 256, 0, s>>>(root, size, nn, (long long)min_size, (long long)max_size, keep);
-            if ((e = xs_exclusive_scan(w + L.temp, keep, keep, nn, s)) != hipSuccess) return (int32_t)e;
+            if ((e = xs_exclusive_scan(L.temp, keep, keep, nn, s)) != hipSuccess) return (int32_t)e;
             ec_label_kernel<<<nblk, 256, 0, s>>>(root, size, keep, nn, (long long)min_size, (long long)max_size,
                                                  reinterpret_cast<long long*>(labels_out), counts_out);
         }

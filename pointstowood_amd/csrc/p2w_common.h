@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/p2w.h"
+#include "p2w_ws.h"
 
 #define P2W_WAVE 64
 

@@ -172,23 +172,23 @@ __global__ __launch_bounds__(256) void edge_gwg_sum_kernel(const float* __restri
     gWg[i] = acc;
 }
 
-inline size_t eb_up(size_t b) { return (b + 255) & ~size_t(255); }
-struct EbLayout { size_t keys_in, keys_out, slot, start, part, wpart, sub, sub_bytes, bytes; int Z, chunks; };
-inline void eb_layout(int E, int n_src, int C1, EbLayout* L) {
+struct EbWs { unsigned long long *keys_in, *keys_out; int *slot, *start; float *part, *wpart; void* sub; size_t sub_bytes; int Z, chunks; };
+inline EbWs eb_carve(P2wArena& a, int E, int n_src, int C1) {
     const size_t n1 = (size_t)(E > 0 ? E : 1);
     const bool v4 = !(C1 & 3);
-    L->Z = run_pieces(E, n_src);
-    L->chunks = p2w_cdiv(E, P2W_EDGE_CHUNK);
-    size_t o = 0;
-    L->keys_in = o;  o += eb_up(8 * n1);
-    L->keys_out = o; o += eb_up(8 * n1);
-    L->slot = o;     o += eb_up(4 * n1);
-    L->start = o;    o += eb_up(4 * ((size_t)n_src + 1));
-    L->part = o;     o += eb_up(run_part_bytes(L->Z, n_src, v4 ? run_panel<4>() : run_panel<1>()));
-    L->wpart = o;    o += eb_up((size_t)L->chunks * 4 * C1 * sizeof(float));
-    const size_t a = p2w_sort_pairs_u64_ws_bytes((int32_t)n1), b = p2w_cell_starts_ws_bytes(n_src);
-    L->sub = o; L->sub_bytes = eb_up(a > b ? a : b); o += L->sub_bytes;
-    L->bytes = o;
+    EbWs W;
+    W.Z = run_pieces(E, n_src);
+    W.chunks = p2w_cdiv(E, P2W_EDGE_CHUNK);
+    W.keys_in = a.take<unsigned long long>(n1);
+    W.keys_out = a.take<unsigned long long>(n1);
+    W.slot = a.take<int>(n1);
+    W.start = a.take<int>((size_t)n_src + 1);
+    W.part = a.take<float>(run_part_floats(W.Z, n_src, v4 ? run_panel<4>() : run_panel<1>()));
+    W.wpart = a.take<float>((size_t)W.chunks * 4 * C1);
+    const size_t s = p2w_sort_pairs_u64_ws_bytes((int32_t)n1), c = p2w_cell_starts_ws_bytes(n_src);
+    W.sub_bytes = P2wArena::up(s > c ? s : c);             // the sort's and the cell table's scratch, in turn
+    W.sub = a.raw(W.sub_bytes);
+    return W;
 }
 inline bool eb_sizes_ok(long long a, long long b, int C1) { return C1 > 0 && a >= 0 && b >= 0 && a < 0x7fffffffll && b < 0x7fffffffll; }
 
@@ -217,9 +217,7 @@ extern "C" int32_t p2w_edge_l1(const float* P, int32_t ldp, const float* rec_src
 
 extern "C" size_t p2w_edge_l1_bwd_ws_bytes(int32_t E, int32_t n_src, int32_t C1) {
     if (!eb_sizes_ok(E, n_src, C1)) return 0;
-    EbLayout L;
-    eb_layout(E, n_src, C1, &L);
-    return L.bytes;
+    return p2w_ws_bytes([&](P2wArena& a) { eb_carve(a, E, n_src, C1); });
 }
 
 extern "C" int32_t p2w_edge_l1_bwd(const float* gH, int32_t ldg, const float* H1, int32_t ldh, const float* geo, const int32_t* src,
@@ -235,26 +233,22 @@ extern "C" int32_t p2w_edge_l1_bwd(const float* gH, int32_t ldg, const float* H1
         if ((ldg & 3) || (ldh & 3) || (ldgp & 3)) return P2W_EALIGN;
         P2W_CHECK_ALIGN16(gH); P2W_CHECK_ALIGN16(H1); P2W_CHECK_ALIGN16(gP); P2W_CHECK_ALIGN16(gWg);
     }
-    EbLayout L;
-    eb_layout(E, n_src, C1, &L);
-    if (ws_bytes < L.bytes) return P2W_EWORKSPACE;
+    P2wArena arena(ws);
+    const EbWs L = eb_carve(arena, E, n_src, C1);
+    if (ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
     hipStream_t s = p2w_s(stream);
-    char* w = static_cast<char*>(ws);
-    auto* keys_in = reinterpret_cast<unsigned long long*>(w + L.keys_in);
-    auto* keys_out = reinterpret_cast<unsigned long long*>(w + L.keys_out);
-    int* slot = reinterpret_cast<int*>(w + L.slot);
-    int* start = reinterpret_cast<int*>(w + L.start);
-    float* part = reinterpret_cast<float*>(w + L.part);
-    float* wpart = reinterpret_cast<float*>(w + L.wpart);
+    unsigned long long *keys_in = L.keys_in, *keys_out = L.keys_out;
+    int *slot = L.slot, *start = L.start;
+    float *part = L.part, *wpart = L.wpart;
     int32_t st;
     if (n_src > 0) {
         if (E > 0) {
             edge_keys_kernel<<<p2w_cdiv(E, 256), 256, 0, s>>>(src, E, n_src, keys_in);
             st = p2w_sort_pairs_u64(reinterpret_cast<const uint64_t*>(keys_in), reinterpret_cast<uint64_t*>(keys_out), nullptr, slot, E,
-                                    w + L.sub, L.sub_bytes, stream);
+                                    L.sub, L.sub_bytes, stream);
             if (st != P2W_OK) return st;
         }
-        st = p2w_cell_starts(reinterpret_cast<const uint64_t*>(keys_out), E, n_src, start, w + L.sub, L.sub_bytes, stream);
+        st = p2w_cell_starts(reinterpret_cast<const uint64_t*>(keys_out), E, n_src, start, L.sub, L.sub_bytes, stream);
         if (st != P2W_OK) return st;
         if (v4) run_sum<4>(EdgeGzTerm<4>{gH, ldg, H1, ldh}, C1, start, slot, n_src, L.Z, part, gP, ldgp, s);
         else run_sum<1>(EdgeGzTerm<1>{gH, ldg, H1, ldh}, C1, start, slot, n_src, L.Z, part, gP, ldgp, s);

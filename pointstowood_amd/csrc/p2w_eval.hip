@@ -31,18 +31,16 @@ constexpr int EV_WAVES = EV_THREADS / P2W_WAVE;
 // the cell grid the chunk pass keeps in registers: classes rounded up to 2, 4 or 8
 inline int ev_pad(int classes) { return classes <= 2 ? 2 : classes <= 4 ? 4 : 8; }
 
-struct EvLayout { size_t first, pcount, psum, total; long long max_chunks; int cells; };
+struct EvWs { long long* first; int* pcount; double* psum; long long max_chunks; int cells; };
 
-EvLayout ev_layout(long long n, int segments, int classes) {
-    auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
-    EvLayout L;
-    L.max_chunks = n / P2W_EVAL_CHUNK + segments;
-    L.cells = ev_pad(classes) * ev_pad(classes);
-    L.first = 0;
-    L.pcount = L.first + up(sizeof(long long) * ((size_t)segments + 1));
-    L.psum = L.pcount + up(sizeof(int) * (size_t)L.max_chunks * (L.cells + 1));      // (+ 1: the chunk's invalid points)
-    L.total = L.psum + up(sizeof(double) * (size_t)L.max_chunks * L.cells);
-    return L;
+EvWs ev_carve(P2wArena& a, long long n, int segments, int classes) {
+    EvWs W;
+    W.max_chunks = n / P2W_EVAL_CHUNK + segments;
+    W.cells = ev_pad(classes) * ev_pad(classes);
+    W.first = a.take<long long>((size_t)segments + 1);
+    W.pcount = a.take<int>((size_t)W.max_chunks * (W.cells + 1));      // (+ 1: the chunk's invalid points)
+    W.psum = a.take<double>((size_t)W.max_chunks * W.cells);
+    return W;
 }
 
 __device__ __forceinline__ long long ev_clamp(long long v, long long n) { return v < 0 ? 0 : v > n ? n : v; }
@@ -254,7 +252,7 @@ void ev_launch_chunks(int pad, int grid, hipStream_t s, const float* truth, cons
 
 extern "C" size_t p2w_confusion_ws_bytes(int64_t n, int32_t segments, int32_t classes) {
     if (n < 0 || segments < 1 || classes < 2 || classes > P2W_EVAL_MAX_CLASSES) return 0;
-    return ev_layout(n, segments, classes).total;
+    return p2w_ws_bytes([&](P2wArena& a) { ev_carve(a, n, segments, classes); });
 }
 
 extern "C" int32_t p2w_confusion(const float* truth, const float* pred, const double* weight, const int64_t* seg_ptr, int64_t n,
@@ -264,10 +262,11 @@ extern "C" int32_t p2w_confusion(const float* truth, const float* pred, const do
     if (segments < 1 || classes < 2 || classes > P2W_EVAL_MAX_CLASSES) return P2W_EINVAL;
     if (seg_ptr == nullptr && segments != 1) return P2W_EINVAL;
     if ((weight == nullptr) != (wsum == nullptr)) return P2W_EINVAL;
-    const EvLayout L = ev_layout(n, segments, classes);
+    P2wArena arena(ws);
+    const EvWs L = ev_carve(arena, n, segments, classes);
     if (L.max_chunks > 0x7fffffff) return P2W_EINVAL;
     P2W_CHECK_PTR(ws); P2W_CHECK_ALIGN16(ws);
-    if (ws_bytes < L.total) return P2W_EWORKSPACE;
+    if (ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
     P2W_CHECK_PTR(counts); P2W_CHECK_PTR(invalid);
     if (n > 0) {
         P2W_CHECK_PTR(truth); P2W_CHECK_PTR(pred);
@@ -275,16 +274,12 @@ extern "C" int32_t p2w_confusion(const float* truth, const float* pred, const do
         if (weight) P2W_CHECK_ALIGN16(weight);
     }
     hipStream_t s = p2w_s(stream);
-    char* w = static_cast<char*>(ws);
-    long long* first = reinterpret_cast<long long*>(w + L.first);
-    int* pcount = reinterpret_cast<int*>(w + L.pcount);
-    double* psum = reinterpret_cast<double*>(w + L.psum);
     const long long* sp = reinterpret_cast<const long long*>(seg_ptr);
     const int pad = ev_pad(classes);
-    ev_table_kernel<<<1, EV_THREADS, 0, s>>>(sp, n, segments, L.max_chunks, first);
-    if (weight) ev_launch_chunks<true>(pad, (int)L.max_chunks, s, truth, pred, weight, sp, first, n, segments, classes, pcount, psum);
-    else ev_launch_chunks<false>(pad, (int)L.max_chunks, s, truth, pred, weight, sp, first, n, segments, classes, pcount, psum);
+    ev_table_kernel<<<1, EV_THREADS, 0, s>>>(sp, n, segments, L.max_chunks, L.first);
+    if (weight) ev_launch_chunks<true>(pad, (int)L.max_chunks, s, truth, pred, weight, sp, L.first, n, segments, classes, L.pcount, L.psum);
+    else ev_launch_chunks<false>(pad, (int)L.max_chunks, s, truth, pred, weight, sp, L.first, n, segments, classes, L.pcount, L.psum);
     ev_sum_kernel<<<dim3((unsigned)segments, (unsigned)(classes * classes + 1)), EV_THREADS, 0, s>>>(
-        first, pcount, psum, classes, pad, reinterpret_cast<long long*>(counts), wsum, reinterpret_cast<long long*>(invalid));
+        L.first, L.pcount, L.psum, classes, pad, reinterpret_cast<long long*>(counts), wsum, reinterpret_cast<long long*>(invalid));
     return P2W_LAUNCH_STATUS();
 }

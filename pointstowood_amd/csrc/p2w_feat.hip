@@ -401,9 +401,11 @@ __global__ __launch_bounds__(256) void rowdot_finish_kernel(const float* __restr
     out[i] = acc + b;
 }
 static inline int rowdot_ldpart(int M) { return (M + 255) / 256 * 256; }
+// one row of ldpart floats per 64-column slice
+static inline float* rowdot_carve(P2wArena& a, int M, int N) { return a.take<float>((size_t)((N + 63) / 64) * rowdot_ldpart(M)); }
 extern "C" size_t p2w_gemm_h2_rowdot_ws_bytes(int32_t M, int32_t N) {
     if (M < 0 || N <= 0) return 0;
-    return (size_t)((N + 63) / 64) * rowdot_ldpart(M) * sizeof(float);
+    return p2w_ws_bytes([&](P2wArena& a) { rowdot_carve(a, M, N); });
 }
 extern "C" int32_t p2w_gemm_h2_rowdot(int32_t prec, const void* A_h, int32_t ldh_a, const void* Wh, float wscale, int32_t M, int32_t N,
                                       int32_t K, const p2w_epilogue* epi, const float* dot_w, float dot_b, float* out, void* ws,
@@ -414,7 +416,9 @@ extern "C" int32_t p2w_gemm_h2_rowdot(int32_t prec, const void* A_h, int32_t ldh
     P2W_CHECK_ALIGN16(A_h); P2W_CHECK_ALIGN16(Wh); P2W_CHECK_ALIGN16(ws);
     if (M < 0 || N <= 0 || K <= 0 || ldh_a < K || !(wscale > 0.f)) return P2W_EINVAL;
     if ((flags & P2W_GEMM_TILE_128) && (flags & P2W_GEMM_TILE_256)) return P2W_EINVAL;
-    if (ws_bytes < p2w_gemm_h2_rowdot_ws_bytes(M, N)) return P2W_EWORKSPACE;
+    P2wArena arena(ws);
+    float* part = rowdot_carve(arena, M, N);
+    if (ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
     EpiArgs ep = {};
     if (epi) {
         if ((epi->sc0 && !epi->sh0) || (epi->sc1 && !epi->sh1)) return P2W_ENULL;
@@ -423,7 +427,6 @@ extern "C" int32_t p2w_gemm_h2_rowdot(int32_t prec, const void* A_h, int32_t ldh
     }
     const _Float16* Ah = static_cast<const _Float16*>(A_h);
     const _Float16* Wp = static_cast<const _Float16*>(Wh);
-    float* part = static_cast<float*>(ws);
     const int ldpart = rowdot_ldpart(M);
     const int32_t rc = prec == P2W_PREC_F16X3
         ? launch_gemm_h<0>(Ah, ldh_a, Wp, wscale, M, N, K, ep, nullptr, 0, nullptr, 0, flags, p2w_s(stream), dot_w, part, ldpart)
@@ -524,7 +527,7 @@ __global__ __launch_bounds__(SA_PART_BLOCK) void sa_part_scatter_kernel(const in
     else if (in) list_large[(blockIdx.x * SA_PART_BLOCK - off_s) + (threadIdx.x - rank_s)] = t;   // stable: earlier large targets
 }
 
-extern "C" size_t p2w_sa_conv_h_ws_bytes(int32_t M, int32_t flags) { return sa_conv_ws_bytes(M < 0 ? 0 : M, flags); }
+extern "C" size_t p2w_sa_conv_h_ws_bytes(int32_t M, int32_t flags) { return p2w_ws_bytes([&](P2wArena& a) { sa_conv_carve(a, M < 0 ? 0 : M, flags); }); }
 
 extern "C" int32_t p2w_sa_conv_h_rows(int32_t prec, const float* P, int32_t ldp, int32_t n_src, const float* xyzr_src, const int32_t* idx,
                                  const int32_t* batch_dst, const float* sf, const int32_t* nbr, const int32_t* deg,

@@ -170,31 +170,24 @@ __global__ __launch_bounds__(256) void vs_scatter_kernel(const int* __restrict__
     }
 }
 
-struct VsLayout { size_t hdr, keys_in, keys_out, vals_in, vals_out, flags, scan, temp, temp_bytes, total; };
-
-static hipError_t vs_layout(int n_bound, VsLayout* L) {
-    auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
-    RsLayout R;
-    rs_layout(n_bound, &R);
-    const size_t sort_bytes = R.bytes, scan_bytes = xs_ws_bytes(n_bound);   // the hand-written sort / scan of p2w_sort.h
-    size_t off = 0;
-    L->hdr = off; off += up(sizeof(VsHeader));
-    L->keys_in = off; off += up(sizeof(unsigned long long) * n_bound);
-    L->keys_out = off; off += up(sizeof(unsigned long long) * (n_bound + 1));
-    L->vals_in = off; off += up(sizeof(int) * n_bound);
-    L->vals_out = off; off += up(sizeof(int) * n_bound);
-    L->flags = off; off += up(sizeof(int) * n_bound);
-    L->scan = off; off += up(sizeof(int) * n_bound);
-    L->temp = off; L->temp_bytes = up(sort_bytes > scan_bytes ? sort_bytes : scan_bytes); off += L->temp_bytes;
-    L->total = off;
-    return hipSuccess;
+struct VsWs { VsHeader* hdr; unsigned long long *keys_in, *keys_out; int *vals_in, *vals_out, *flags, *scan; void* temp; };
+static VsWs vs_carve(P2wArena& a, int n_bound) {
+    const size_t n = (size_t)n_bound, sort_bytes = rs_ws_bytes(n_bound), scan_bytes = xs_ws_bytes(n_bound);
+    VsWs W;
+    W.hdr = a.take<VsHeader>(1);
+    W.keys_in = a.take<unsigned long long>(n);
+    W.keys_out = a.take<unsigned long long>(n + 1);
+    W.vals_in = a.take<int>(n);
+    W.vals_out = a.take<int>(n);
+    W.flags = a.take<int>(n);
+    W.scan = a.take<int>(n);
+    W.temp = a.raw(sort_bytes > scan_bytes ? sort_bytes : scan_bytes);   // the hand-written sort / scan of p2w_sort.h, in turn
+    return W;
 }
 
 extern "C" size_t p2w_voxel_sample_ws_bytes(int32_t n_bound) {
     if (n_bound <= 0) return 256;
-    VsLayout L;
-    if (vs_layout(n_bound, &L) != hipSuccess) return 0;
-    return L.total;
+    return p2w_ws_bytes([&](P2wArena& a) { vs_carve(a, n_bound); });
 }
 
 // min/max + keys into keys_out[n_bound] (padding keys = ~0)
@@ -208,27 +201,24 @@ static int32_t vs_compute_keys(const float4* x4, const int* ptr, int B, int n_bo
 }
 
 // sort (key, point) pairs, flag the last element of each run, compact
-static int32_t vs_cluster(char* w, const VsLayout& L, const unsigned long long* keys_in, const int* ptr, int B,
+static int32_t vs_cluster(const VsWs& L, const unsigned long long* keys_in, const int* ptr, int B,
                           const int* n_dev, int n_bound, int* idx_out, int* ptr_out, int* batch_out, int* inv_out,
                           int* count_out, int* order_out, int* rank_sorted_out, unsigned long long* sorted_keys_out,
                           unsigned long long* cell_keys_out, float res, p2w_grid* grid_out, hipStream_t s) {
-    auto* keys_out = reinterpret_cast<unsigned long long*>(w + L.keys_out);
-    int* vals_in = reinterpret_cast<int*>(w + L.vals_in);
-    int* vals_out = reinterpret_cast<int*>(w + L.vals_out);
-    int* flags = reinterpret_cast<int*>(w + L.flags);
-    int* scan = reinterpret_cast<int*>(w + L.scan);
+    unsigned long long* keys_out = L.keys_out;
+    int *vals_in = L.vals_in, *vals_out = L.vals_out, *flags = L.flags, *scan = L.scan;
     const int nblk = p2w_cdiv(n_bound, 256);
     // stable radix sort of the (key, point) pairs: only the valid ones (the padding keys beyond *n_dev stay where they are and
     // would make every one of the eight digit passes run), then flags -> ranks
-    hipError_t e = rs_sort_pairs(w + L.temp, keys_in, keys_out, vals_in, vals_out, n_dev, n_bound, s);
+    hipError_t e = rs_sort_pairs(L.temp, keys_in, keys_out, vals_in, vals_out, n_dev, n_bound, s);
     if (e != hipSuccess) return (int32_t)e;
     vs_flags_kernel<<<nblk, 256, 0, s>>>(keys_out, n_dev, n_bound, flags);
-    e = xs_exclusive_scan(w + L.temp, flags, scan, n_bound, s);
+    e = xs_exclusive_scan(L.temp, flags, scan, n_bound, s);
     if (e != hipSuccess) return (int32_t)e;
     const int nblk2 = p2w_cdiv((n_bound > B + 1 ? n_bound : B + 1), 256);
     vs_scatter_kernel<<<nblk2, 256, 0, s>>>(flags, scan, vals_out, ptr, B, n_dev, n_bound, idx_out, ptr_out, batch_out,
                                             inv_out, count_out, order_out, rank_sorted_out, keys_out, sorted_keys_out, cell_keys_out,
-                                            reinterpret_cast<const VsHeader*>(w + L.hdr), res, grid_out);
+                                            L.hdr, res, grid_out);
     return P2W_LAUNCH_STATUS();
 }
 
@@ -242,16 +232,12 @@ extern "C" int32_t p2w_voxel_sample(const float* xyzr, const int32_t* ptr, int32
     if (n_bound == 0) return (int32_t)hipMemsetAsync(ptr_out, 0, sizeof(int) * (B + 1), s);
     P2W_CHECK_PTR(xyzr); P2W_CHECK_PTR(idx_out); P2W_CHECK_PTR(batch_out); P2W_CHECK_PTR(ws);
     P2W_CHECK_ALIGN16(xyzr); P2W_CHECK_ALIGN16(ws);
-    VsLayout L;
-    hipError_t e = vs_layout(n_bound, &L);
-    if (e != hipSuccess) return (int32_t)e;
-    if (ws_bytes < L.total) return P2W_EWORKSPACE;
-    char* w = static_cast<char*>(ws);
-    auto* keys_in = reinterpret_cast<unsigned long long*>(w + L.keys_in);
-    int32_t st = vs_compute_keys(reinterpret_cast<const float4*>(xyzr), ptr, B, n_bound, res,
-                                 reinterpret_cast<VsHeader*>(w + L.hdr), keys_in, reinterpret_cast<int*>(w + L.vals_in), s);
+    P2wArena arena(ws);
+    const VsWs L = vs_carve(arena, n_bound);
+    if (ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
+    int32_t st = vs_compute_keys(reinterpret_cast<const float4*>(xyzr), ptr, B, n_bound, res, L.hdr, L.keys_in, L.vals_in, s);
     if (st != P2W_OK) return st;
-    return vs_cluster(w, L, keys_in, ptr, B, ptr + B, n_bound, idx_out, ptr_out, batch_out, inv_out, nullptr, order_out,
+    return vs_cluster(L, L.keys_in, ptr, B, ptr + B, n_bound, idx_out, ptr_out, batch_out, inv_out, nullptr, order_out,
                       rank_sorted_out, reinterpret_cast<unsigned long long*>(sorted_keys_out),
                       reinterpret_cast<unsigned long long*>(cell_keys_out), res, grid_out, s);
 }
@@ -274,14 +260,12 @@ extern "C" int32_t p2w_consecutive_cluster(const int64_t* cell, int32_t n, int32
     if (n == 0) return (int32_t)hipMemsetAsync(count_out, 0, sizeof(int), s);
     P2W_CHECK_PTR(cell); P2W_CHECK_PTR(perm_out); P2W_CHECK_PTR(ws); P2W_CHECK_ALIGN16(ws);
     if (n < 0) return P2W_EINVAL;
-    VsLayout L;
-    hipError_t e = vs_layout(n, &L);
-    if (e != hipSuccess) return (int32_t)e;
-    if (ws_bytes < L.total) return P2W_EWORKSPACE;
-    char* w = static_cast<char*>(ws);
-    vs_iota_kernel<<<p2w_cdiv(n, 256), 256, 0, s>>>(n, reinterpret_cast<int*>(w + L.vals_in));
+    P2wArena arena(ws);
+    const VsWs L = vs_carve(arena, n);
+    if (ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
+    vs_iota_kernel<<<p2w_cdiv(n, 256), 256, 0, s>>>(n, L.vals_in);
     // non-negative int64 cell ids order like their unsigned bit patterns
-    return vs_cluster(w, L, reinterpret_cast<const unsigned long long*>(cell), nullptr, 0, nullptr, n, perm_out, nullptr,
+    return vs_cluster(L, reinterpret_cast<const unsigned long long*>(cell), nullptr, 0, nullptr, n, perm_out, nullptr,
                       nullptr, inv_out, count_out, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, s);
 }
 
@@ -569,43 +553,40 @@ __global__ __launch_bounds__(256) void tk_finish_kernel(const int* __restrict__ 
         tk_points_body((int)t, key32, rank, bs_occ, off, bs_cnt, fill, ptr, B, n_bound, inv_out, order_out, sorted_keys_out, rank_sorted_out, status);
 }
 
-struct TkLayout { size_t hdr, key32, bs_occ, bs_cnt, total, tab_max, rank, cnt, off, fill, bytes; long long T_cap; int nblk; };
-static void tk_layout(int n_bound, long long T_cap, TkLayout* L) {
-    auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
-    L->T_cap = T_cap;
-    L->nblk = (int)((T_cap + TK_TILE - 1) / TK_TILE);
-    size_t o = 0;
-    L->hdr = o; o += up(sizeof(VsHeader));
-    L->total = o; o += 256;
-    L->key32 = o; o += up(sizeof(int) * (size_t)n_bound);
-    L->bs_occ = o; o += up(sizeof(int) * (size_t)L->nblk);
-    L->bs_cnt = o; o += up(sizeof(int) * (size_t)L->nblk);
-    L->tab_max = o; o += up(sizeof(int) * (size_t)T_cap);
-    L->cnt = o; o += up(sizeof(int) * (size_t)T_cap);
-    L->fill = o; o += up(sizeof(int) * (size_t)T_cap);
-    L->rank = o; o += up(sizeof(int) * (size_t)T_cap);
-    L->off = o; o += up(sizeof(int) * (size_t)T_cap);
-    L->bytes = o;
+struct TkWs { VsHeader* hdr; int *total, *key32, *bs_occ, *bs_cnt, *tab_max, *cnt, *fill, *rank, *off; int nblk; };
+// hdr and the 256-byte `total` block come first and depend on neither size: p2w_voxel_sample_table_prepare() finds them
+// through tk_carve(a, 0, 0) without knowing the sizes its workspace was made for.
+static TkWs tk_carve(P2wArena& a, int n_bound, long long T_cap) {
+    TkWs W;
+    W.nblk = (int)((T_cap + TK_TILE - 1) / TK_TILE);
+    W.hdr = a.take<VsHeader>(1);
+    W.total = a.take<int>(64);       // [0] the total, [16] the scan's completion counter, [32..] the second bounding box
+    W.key32 = a.take<int>((size_t)n_bound);
+    W.bs_occ = a.take<int>((size_t)W.nblk);
+    W.bs_cnt = a.take<int>((size_t)W.nblk);
+    W.tab_max = a.take<int>((size_t)T_cap);
+    W.cnt = a.take<int>((size_t)T_cap);
+    W.fill = a.take<int>((size_t)T_cap);
+    W.rank = a.take<int>((size_t)T_cap);
+    W.off = a.take<int>((size_t)T_cap);
+    return W;
 }
 
 extern "C" size_t p2w_voxel_sample_table_ws_bytes(int32_t n_bound, int64_t table_cells) {
     if (n_bound < 0 || table_cells <= 0 || table_cells > ((int64_t)1 << 30)) return 0;
-    TkLayout L;
-    tk_layout(n_bound > 0 ? n_bound : 1, table_cells, &L);
-    return L.bytes;
+    return p2w_ws_bytes([&](P2wArena& a) { tk_carve(a, n_bound > 0 ? n_bound : 1, table_cells); });
 }
 
 // Workspace state between calls (p2w_voxel_sample_table_prepared): bounding-box words at their atomics' identities, the scan's
 // completion counter at zero.  p2w_voxel_sample_table_prepare() establishes it on a fresh workspace, every call restores it.
 extern "C" int32_t p2w_voxel_sample_table_prepare(void* ws, size_t ws_bytes, p2w_stream_t stream) {
     P2W_CHECK_PTR(ws); P2W_CHECK_ALIGN16(ws);
-    TkLayout L;
-    tk_layout(1, 1, &L);
-    if (ws_bytes < L.total + 256) return P2W_EWORKSPACE;
-    char* w = static_cast<char*>(ws);
-    hipError_t e = hipMemsetAsync(w + L.total, 0, 256, p2w_s(stream));
+    P2wArena arena(ws);
+    const TkWs L = tk_carve(arena, 0, 0);                    // hdr and total alone
+    if (ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
+    hipError_t e = hipMemsetAsync(L.total, 0, 256, p2w_s(stream));
     if (e != hipSuccess) return (int32_t)e;
-    vs_init_kernel<<<1, 64, 0, p2w_s(stream)>>>(reinterpret_cast<VsHeader*>(w + L.hdr));
+    vs_init_kernel<<<1, 64, 0, p2w_s(stream)>>>(L.hdr);
     return P2W_LAUNCH_STATUS();
 }
 
@@ -627,24 +608,16 @@ static int32_t voxel_sample_table_impl(bool prepared, const float* xyzr, const i
     P2W_CHECK_PTR(xyzr); P2W_CHECK_PTR(idx_out); P2W_CHECK_PTR(batch_out); P2W_CHECK_PTR(ws);
     P2W_CHECK_ALIGN16(xyzr); P2W_CHECK_ALIGN16(ws);
     if ((sorted_keys_out || rank_sorted_out) && !order_out) return P2W_ENULL;
-    TkLayout L;
-    tk_layout(n_bound, table_cells, &L);
-    if (ws_bytes < L.bytes) return P2W_EWORKSPACE;
+    P2wArena arena(ws);
+    const TkWs L = tk_carve(arena, n_bound, table_cells);
+    if (ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
     if (!prepared) {
         const int32_t rc = p2w_voxel_sample_table_prepare(ws, ws_bytes, stream);
         if (rc != P2W_OK) return rc;
     }
-    char* w = static_cast<char*>(ws);
-    auto* hdr = reinterpret_cast<VsHeader*>(w + L.hdr);
-    int* tab_max = reinterpret_cast<int*>(w + L.tab_max);
-    int* cnt = order_out ? reinterpret_cast<int*>(w + L.cnt) : nullptr;
-    int* fill = reinterpret_cast<int*>(w + L.fill);
-    int* rank = reinterpret_cast<int*>(w + L.rank);
-    int* off = reinterpret_cast<int*>(w + L.off);
-    int* key32 = reinterpret_cast<int*>(w + L.key32);
-    int* bs_occ = reinterpret_cast<int*>(w + L.bs_occ);
-    int* bs_cnt = reinterpret_cast<int*>(w + L.bs_cnt);
-    int* total = reinterpret_cast<int*>(w + L.total);
+    VsHeader* hdr = L.hdr;
+    int *tab_max = L.tab_max, *cnt = order_out ? L.cnt : nullptr, *fill = L.fill, *rank = L.rank, *off = L.off;
+    int *key32 = L.key32, *bs_occ = L.bs_occ, *bs_cnt = L.bs_cnt, *total = L.total;
     int* done = total + 16;                                  // the scan's completion counter (zero between calls)
     const auto* x4 = reinterpret_cast<const float4*>(xyzr);
     const int nblk_pts = p2w_cdiv(n_bound, 256);
@@ -1730,24 +1703,18 @@ __global__ __launch_bounds__(256) void morton_keys_kernel(const float4* __restri
     if (vals) vals[i] = i;
 }
 
-struct MoLayout { size_t keys_in, keys_out, temp, temp_bytes, total; };
-static hipError_t mo_layout(int n, MoLayout* L) {
-    auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
-    RsLayout R;
-    rs_layout(n, &R);
-    size_t off = 0;
-    L->keys_in = off; off += up(sizeof(unsigned long long) * n);
-    L->keys_out = off; off += up(sizeof(unsigned long long) * n);
-    L->temp = off; L->temp_bytes = up(R.bytes); off += L->temp_bytes;
-    L->total = off;
-    return hipSuccess;
+struct MoWs { unsigned long long *keys_in, *keys_out; void* temp; };
+static MoWs mo_carve(P2wArena& a, int n) {
+    MoWs W;
+    W.keys_in = a.take<unsigned long long>((size_t)n);
+    W.keys_out = a.take<unsigned long long>((size_t)n);
+    W.temp = a.raw(rs_ws_bytes(n));
+    return W;
 }
 
 extern "C" size_t p2w_morton_order_ws_bytes(int32_t n) {
     if (n <= 0) return 256;
-    MoLayout L;
-    if (mo_layout(n, &L) != hipSuccess) return 0;
-    return L.total;
+    return p2w_ws_bytes([&](P2wArena& a) { mo_carve(a, n); });
 }
 
 extern "C" int32_t p2w_morton_order(const float* xyzr, int32_t n, const p2w_grid* grid, int32_t* order_out, void* ws,
@@ -1756,16 +1723,13 @@ extern "C" int32_t p2w_morton_order(const float* xyzr, int32_t n, const p2w_grid
     P2W_CHECK_PTR(xyzr); P2W_CHECK_PTR(grid); P2W_CHECK_PTR(order_out); P2W_CHECK_PTR(ws);
     P2W_CHECK_ALIGN16(xyzr); P2W_CHECK_ALIGN16(ws);
     if (n < 0) return P2W_EINVAL;
-    MoLayout L;
-    hipError_t e = mo_layout(n, &L);
-    if (e != hipSuccess) return (int32_t)e;
-    if (ws_bytes < L.total) return P2W_EWORKSPACE;
-    char* w = static_cast<char*>(ws);
+    P2wArena arena(ws);
+    const MoWs L = mo_carve(arena, n);
+    if (ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
     hipStream_t s = p2w_s(stream);
-    auto* keys_in = reinterpret_cast<unsigned long long*>(w + L.keys_in);
-    morton_keys_kernel<<<p2w_cdiv(n, 256), 256, 0, s>>>(reinterpret_cast<const float4*>(xyzr), n, grid, keys_in, nullptr);
+    morton_keys_kernel<<<p2w_cdiv(n, 256), 256, 0, s>>>(reinterpret_cast<const float4*>(xyzr), n, grid, L.keys_in, nullptr);
     // argsort (values = 0..n-1) by the hand-written radix sort: as many digit passes as the largest key has bytes
-    e = rs_sort_pairs(w + L.temp, keys_in, reinterpret_cast<unsigned long long*>(w + L.keys_out), nullptr, order_out, nullptr, n, s);
+    const hipError_t e = rs_sort_pairs(L.temp, L.keys_in, L.keys_out, nullptr, order_out, nullptr, n, s);
     if (e != hipSuccess) return (int32_t)e;
     return P2W_LAUNCH_STATUS();
 }
@@ -1851,9 +1815,7 @@ extern "C" int32_t p2w_cells_nd(const float* P, int32_t n, int32_t D, int32_t ld
 }
 
 extern "C" size_t p2w_sort_pairs_u64_ws_bytes(int32_t n) {
-    RsLayout R;
-    rs_layout(n > 0 ? n : 1, &R);
-    return R.bytes;
+    return rs_ws_bytes(n);
 }
 extern "C" int32_t p2w_sort_pairs_u64(const uint64_t* keys_in, uint64_t* keys_out, const int32_t* vals_in, int32_t* vals_out, int32_t n,
                                       void* ws, size_t ws_bytes, p2w_stream_t stream) {
@@ -1894,10 +1856,19 @@ __global__ __launch_bounds__(256) void vr_compact_kernel(const int* __restrict__
     starts_out[pos[r]] = run_start[r];
     counts_out[pos[r]] = run_start[r + 1] - run_start[r];
 }
-extern "C" size_t p2w_key_runs_ws_bytes(int32_t n) {
+struct VrWs { int *a, *b, *run_start, *n_runs; void* xs; };
+static VrWs vr_carve(P2wArena& ar, int n) {
     const size_t m = (size_t)(n > 0 ? n : 1) + 1;
-    return 4 * ((m * sizeof(int) + 255) & ~size_t(255)) + 256 + xs_ws_bytes(n);
+    VrWs W;
+    W.a = ar.take<int>(m);             // run-start flags, then keep flags
+    W.b = ar.take<int>(m);             // their exclusive scans
+    W.run_start = ar.take<int>(m);
+    W.n_runs = ar.take<int>(1);
+    W.xs = ar.raw(xs_ws_bytes(n), 1);
+    ar.raw(m * sizeof(int));           // slack: a fourth array's worth that the size has always counted
+    return W;
 }
+extern "C" size_t p2w_key_runs_ws_bytes(int32_t n) { return p2w_ws_bytes([&](P2wArena& a) { vr_carve(a, n); }); }
 extern "C" int32_t p2w_key_runs(const uint64_t* keys_sorted, int32_t n, int32_t min_count, int32_t* starts_out, int32_t* counts_out,
                                 int32_t* n_out, void* ws, size_t ws_bytes, p2w_stream_t stream) {
     P2W_CHECK_PTR(n_out);
@@ -1905,14 +1876,11 @@ extern "C" int32_t p2w_key_runs(const uint64_t* keys_sorted, int32_t n, int32_t 
     if (n == 0) return (int32_t)hipMemsetAsync(n_out, 0, sizeof(int), s);
     P2W_CHECK_PTR(keys_sorted); P2W_CHECK_PTR(starts_out); P2W_CHECK_PTR(counts_out); P2W_CHECK_PTR(ws); P2W_CHECK_ALIGN16(ws);
     if (n < 0) return P2W_EINVAL;
-    if (ws_bytes < p2w_key_runs_ws_bytes(n)) return P2W_EWORKSPACE;
-    const size_t seg = (((size_t)n + 1) * sizeof(int) + 255) & ~size_t(255);
-    char* w = static_cast<char*>(ws);
-    int* a = reinterpret_cast<int*>(w);             // run-start flags, then keep flags
-    int* b = reinterpret_cast<int*>(w + seg);       // their exclusive scans
-    int* run_start = reinterpret_cast<int*>(w + 2 * seg);
-    int* n_runs = reinterpret_cast<int*>(w + 3 * seg);
-    void* xs = w + 3 * seg + 256;
+    P2wArena arena(ws);
+    const VrWs L = vr_carve(arena, n);
+    if (ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
+    int *a = L.a, *b = L.b, *run_start = L.run_start, *n_runs = L.n_runs;
+    void* xs = L.xs;
     const int nblk = p2w_cdiv(n, 256);
     const auto* k = reinterpret_cast<const unsigned long long*>(keys_sorted);
     vr_flag_kernel<<<nblk, 256, 0, s>>>(k, n, a);

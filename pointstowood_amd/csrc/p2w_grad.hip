@@ -184,21 +184,21 @@ struct InterpTerm {
     }
 };
 
-inline size_t ib_up(size_t b) { return (b + 255) & ~size_t(255); }
-struct IbLayout { size_t keys_in, keys_out, slot, wgt, start, part, sub, sub_bytes, bytes; int Z; };
-inline void ib_layout(long long N, int n_coarse, IbLayout* L) {
+struct IbWs { unsigned long long *keys_in, *keys_out; int* slot; float* wgt; int* start; float* part; void* sub; size_t sub_bytes; int Z; };
+inline IbWs ib_carve(P2wArena& a, long long N, int n_coarse) {
     const size_t n1 = (size_t)(N > 0 ? N : 1);
-    L->Z = run_pieces(N, n_coarse);
-    size_t o = 0;
-    L->keys_in = o;  o += ib_up(8 * n1);
-    L->keys_out = o; o += ib_up(8 * n1);
-    L->slot = o;     o += ib_up(4 * n1);
-    L->wgt = o;      o += ib_up(4 * n1);
-    L->start = o;    o += ib_up(4 * ((size_t)n_coarse + 1));
-    L->part = o;     o += ib_up(run_part_bytes(L->Z, n_coarse, run_panel<4>()));
-    const size_t a = p2w_sort_pairs_u64_ws_bytes((int32_t)n1), b = p2w_cell_starts_ws_bytes(n_coarse);
-    L->sub = o; L->sub_bytes = ib_up(a > b ? a : b); o += L->sub_bytes;
-    L->bytes = o;
+    IbWs W;
+    W.Z = run_pieces(N, n_coarse);
+    W.keys_in = a.take<unsigned long long>(n1);
+    W.keys_out = a.take<unsigned long long>(n1);
+    W.slot = a.take<int>(n1);
+    W.wgt = a.take<float>(n1);
+    W.start = a.take<int>((size_t)n_coarse + 1);
+    W.part = a.take<float>(run_part_floats(W.Z, n_coarse, run_panel<4>()));
+    const size_t s = p2w_sort_pairs_u64_ws_bytes((int32_t)n1), c = p2w_cell_starts_ws_bytes(n_coarse);
+    W.sub_bytes = P2wArena::up(s > c ? s : c);             // the sort's and the cell table's scratch, in turn
+    W.sub = a.raw(W.sub_bytes);
+    return W;
 }
 
 }  // namespace
@@ -243,9 +243,7 @@ extern "C" int32_t p2w_segment_max_bwd(const float* grad_out, int32_t ldg, const
 
 extern "C" size_t p2w_interp_bwd_ws_bytes(int32_t m, int32_t kw, int32_t n_coarse) {
     if (m < 0 || kw < 1 || kw > P2W_MAX_K_WIDE || n_coarse < 0 || (long long)m * kw > 0x7fffffffll) return 0;
-    IbLayout L;
-    ib_layout((long long)m * kw, n_coarse, &L);
-    return L.bytes;
+    return p2w_ws_bytes([&](P2wArena& a) { ib_carve(a, (long long)m * kw, n_coarse); });
 }
 
 extern "C" int32_t p2w_interp_bwd(const float* grad_out, int32_t ldg, int32_t F, const float* xyzr_c, const float* xyzr_f,
@@ -257,27 +255,23 @@ extern "C" int32_t p2w_interp_bwd(const float* grad_out, int32_t ldg, int32_t F,
     P2W_CHECK_ALIGN16(grad_out); P2W_CHECK_ALIGN16(xyzr_c); P2W_CHECK_ALIGN16(xyzr_f); P2W_CHECK_ALIGN16(grad_x); P2W_CHECK_ALIGN16(ws);
     if (m < 0 || n_coarse < 0 || kw < 1 || kw > P2W_MAX_K_WIDE || (long long)m * kw > 0x7fffffffll) return P2W_EINVAL;
     if (F <= 0 || (F & 3) || (ldg & 3) || (ldx & 3) || ldg < F || ldx < F) return P2W_EINVAL;
-    IbLayout L;
     const int N = m * kw;
-    ib_layout(N, n_coarse, &L);
-    if (ws_bytes < L.bytes) return P2W_EWORKSPACE;
+    P2wArena arena(ws);
+    const IbWs L = ib_carve(arena, N, n_coarse);
+    if (ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
     hipStream_t s = p2w_s(stream);
-    char* w = static_cast<char*>(ws);
-    auto* keys_in = reinterpret_cast<unsigned long long*>(w + L.keys_in);
-    auto* keys_out = reinterpret_cast<unsigned long long*>(w + L.keys_out);
-    int* slot = reinterpret_cast<int*>(w + L.slot);
-    float* wgt = reinterpret_cast<float*>(w + L.wgt);
-    int* start = reinterpret_cast<int*>(w + L.start);
-    float* part = reinterpret_cast<float*>(w + L.part);
+    unsigned long long *keys_in = L.keys_in, *keys_out = L.keys_out;
+    int *slot = L.slot, *start = L.start;
+    float *wgt = L.wgt, *part = L.part;
     int32_t st;
     if (N > 0) {
         interp_bwd_prep_kernel<<<p2w_cdiv(m, 256), 256, 0, s>>>(reinterpret_cast<const float4*>(xyzr_c), reinterpret_cast<const float4*>(xyzr_f),
                                                                 nbr, deg, kw, m, n_coarse, keys_in, wgt);
         st = p2w_sort_pairs_u64(reinterpret_cast<const uint64_t*>(keys_in), reinterpret_cast<uint64_t*>(keys_out), nullptr, slot, N,
-                                w + L.sub, L.sub_bytes, stream);
+                                L.sub, L.sub_bytes, stream);
         if (st != P2W_OK) return st;
     }
-    st = p2w_cell_starts(reinterpret_cast<const uint64_t*>(keys_out), N, n_coarse, start, w + L.sub, L.sub_bytes, stream);
+    st = p2w_cell_starts(reinterpret_cast<const uint64_t*>(keys_out), N, n_coarse, start, L.sub, L.sub_bytes, stream);
     if (st != P2W_OK) return st;
     run_sum<4>(InterpTerm{grad_out, ldg, wgt, kw}, F, start, slot, n_coarse, L.Z, part, grad_x, ldx, s);
     return P2W_LAUNCH_STATUS();

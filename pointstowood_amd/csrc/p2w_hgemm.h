@@ -1397,11 +1397,33 @@ __global__ __launch_bounds__(SA_PART_BLOCK) void sa_part_scatter_kernel(const in
 
 // workspace of p2w_sa_conv_h: per-row metadata (20 B per row of a 32-row tile) + tile descriptors; with P2W_SA_PACK8 both
 // target classes have their own rows (worst case: every target in either class), the two target lists and the partition's counters
-static inline size_t sa_conv_ws_bytes(long M, int flags) {
-    const long tiles32 = M, tiles8 = (M + 3) / 4;
-    if (!(flags & P2W_SA_PACK8)) return (size_t)(tiles32 * 32 * 20 + tiles32 * 4 + 256);
-    const long nblk = (M + SA_PART_BLOCK - 1) / SA_PART_BLOCK;
-    return (size_t)((tiles32 + tiles8) * 32 * 20 + (tiles32 + tiles8 * 4) * 4 + 2 * M * 4 + nblk * 4 + 64 + 1024);
+// It is packed, not 256-aligned: every array starts where the one before it ends (all sizes are multiples of 4 bytes, those
+// in front of a float4 array multiples of 16).  Without P2W_SA_PACK8 there are no small-class tiles (t8 = 0) and no lists.
+struct SaWs {
+    float4 *mg_l, *mg_s;                          // per-row geometry of the large / small class
+    int *mj_l, *mj_s, *desc_l, *desc_s;           // per-row source offsets, tile descriptors
+    int *list_s, *list_l, *blk, *counts;          // P2W_SA_PACK8: the two target lists, the partition's block counters and
+    long t32, t8, nblk;                           //   counts: [0] small targets, [1] large targets, [2] / [3] their tiles
+};
+static inline SaWs sa_conv_carve(P2wArena& a, long M, int flags) {
+    const bool pack8 = (flags & P2W_SA_PACK8) != 0;
+    SaWs W = {};
+    W.t32 = M;
+    W.t8 = pack8 ? (M + 3) / 4 : 0;
+    W.nblk = pack8 ? (M + SA_PART_BLOCK - 1) / SA_PART_BLOCK : 0;
+    W.mg_l = a.take<float4>((size_t)W.t32 * 32, 16);
+    W.mg_s = a.take<float4>((size_t)W.t8 * 32, 16);
+    W.mj_l = a.take<int>((size_t)W.t32 * 32, 4);
+    W.mj_s = a.take<int>((size_t)W.t8 * 32, 4);
+    W.desc_l = a.take<int>((size_t)W.t32, 4);
+    W.desc_s = a.take<int>((size_t)W.t8 * 4, 4);
+    if (!pack8) { a.raw(256, 1); return W; }      // slack
+    W.list_s = a.take<int>((size_t)M, 4);
+    W.list_l = a.take<int>((size_t)M, 4);
+    W.blk = a.take<int>((size_t)W.nblk, 4);
+    W.counts = a.take<int>(16, 4);
+    a.raw(1024, 1);                               // slack
+    return W;
 }
 
 // host side of p2w_sa_conv_h for one precision (pointer / size checks are done by the caller)
@@ -1417,7 +1439,9 @@ static int32_t launch_sa_conv_h(const float* P, int32_t ldp, int32_t n_src, cons
     // LDS tables (layer-1 geometry weights, per-column epilogue parameters) and 32-bit offsets: edge rows, P rows in float4 units
     if (C1pad > 512 || C2 > SA_EPI_COLS || (long)M >= (1L << 25) || ((long)n_src + 1) * (ldp / 4) >= (1L << 31)) return P2W_EUNSUPPORTED;   // (descriptors hold target << 6)
     if (ldp < C1pad) return P2W_EINVAL;   // P rows are read in whole K slabs: pad columns (zero) must exist
-    if (ws == nullptr || ws_bytes < sa_conv_ws_bytes(M, flags)) return P2W_EWORKSPACE;
+    P2wArena arena(ws);
+    const SaWs L = sa_conv_carve(arena, M, flags);
+    if (ws == nullptr || ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
     if (reinterpret_cast<uintptr_t>(ws) & 15u) return P2W_EALIGN;
     const int n_cu = p2w_cu_count();
     // 256-column items halve the A production per output column; measured on levels 2 / 3 (C2 = 256 / 512): 2.73 vs 2.82-2.97 ms
@@ -1446,33 +1470,19 @@ static int32_t launch_sa_conv_h(const float* P, int32_t ldp, int32_t n_src, cons
                 P, ldp, meta_j, meta_g, desc, tiles_dev, (int)tiles_max, w1r4, C1, C1pad, W2h, (size_t)C2pad * C1pad, wscale, C2, nMt3,
                 nNt3, b2, bn_s, bn_t, out, ldo, out_h2, ldh, range);
     };
-    char* w = static_cast<char*>(ws);
     if (!(flags & P2W_SA_PACK8)) {
-        float4* meta_g = reinterpret_cast<float4*>(w);
-        int* meta_j = reinterpret_cast<int*>(meta_g + (size_t)M * 32);
-        int* desc = meta_j + (size_t)M * 32;
-        run(std::integral_constant<int, 32>{}, nullptr, nullptr, nullptr, M, meta_g, meta_j, desc);
+        run(std::integral_constant<int, 32>{}, nullptr, nullptr, nullptr, M, L.mg_l, L.mj_l, L.desc_l);
         return P2W_LAUNCH_STATUS();
     }
     // P2W_SA_PACK8: targets with at most 8 neighbours (the sparse ball-query level) share a 32-row MFMA tile four at a time,
     // the others keep a tile each.  Stable partition on the device (no host synchronisation: the kernels read their tile
     // counts from `counts`), then one pre-pass + persistent kernel per class.
-    const long t32 = M, t8 = (M + 3) / 4, nblk = p2w_cdiv(M, SA_PART_BLOCK);
-    float4* mg_l = reinterpret_cast<float4*>(w);            w += t32 * 32 * 16;
-    float4* mg_s = reinterpret_cast<float4*>(w);            w += t8 * 32 * 16;
-    int* mj_l = reinterpret_cast<int*>(w);                  w += t32 * 32 * 4;
-    int* mj_s = reinterpret_cast<int*>(w);                  w += t8 * 32 * 4;
-    int* desc_l = reinterpret_cast<int*>(w);                w += t32 * 4;
-    int* desc_s = reinterpret_cast<int*>(w);                w += t8 * 4 * 4;
-    int* list_s = reinterpret_cast<int*>(w);                w += (size_t)M * 4;
-    int* list_l = reinterpret_cast<int*>(w);                w += (size_t)M * 4;
-    int* blk = reinterpret_cast<int*>(w);                   w += nblk * 4;
-    int* counts = reinterpret_cast<int*>(w);   // [0] small targets, [1] large targets, [2] tiles of small targets, [3] tiles of large targets
-    sa_part_count_kernel<<<(int)nblk, SA_PART_BLOCK, 0, stream>>>(deg, kw, M, blk);
-    sa_part_scan_kernel<<<1, 1024, 0, stream>>>(blk, (int)nblk, M, counts);
-    sa_part_scatter_kernel<<<(int)nblk, SA_PART_BLOCK, 0, stream>>>(deg, kw, M, blk, list_s, list_l);
-    run(std::integral_constant<int, 8>{}, list_s, counts + 0, counts + 2, t8, mg_s, mj_s, desc_s);
-    run(std::integral_constant<int, 32>{}, list_l, counts + 1, counts + 3, t32, mg_l, mj_l, desc_l);
+    int* counts = L.counts;
+    sa_part_count_kernel<<<(int)L.nblk, SA_PART_BLOCK, 0, stream>>>(deg, kw, M, L.blk);
+    sa_part_scan_kernel<<<1, 1024, 0, stream>>>(L.blk, (int)L.nblk, M, counts);
+    sa_part_scatter_kernel<<<(int)L.nblk, SA_PART_BLOCK, 0, stream>>>(deg, kw, M, L.blk, L.list_s, L.list_l);
+    run(std::integral_constant<int, 8>{}, L.list_s, counts + 0, counts + 2, L.t8, L.mg_s, L.mj_s, L.desc_s);
+    run(std::integral_constant<int, 32>{}, L.list_l, counts + 1, counts + 3, L.t32, L.mg_l, L.mj_l, L.desc_l);
     return P2W_LAUNCH_STATUS();
 }
 

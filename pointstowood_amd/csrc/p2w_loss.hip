@@ -199,12 +199,17 @@ void lf_launch(int wmode, unsigned grid, hipStream_t s, const float* logits, con
     else lf_element_kernel<GRAD, 2><<<grid, LF_THREADS, 0, s>>>(logits, labels, weight, n, P, loss, dloss, partial);
 }
 
+// one partial sum per chunk
+double* lf_carve(P2wArena& a, long long n) {
+    const size_t chunks = (size_t)lf_chunks(n);
+    return a.take<double>(chunks ? chunks : 1);
+}
+
 }  // namespace
 
 extern "C" size_t p2w_poly1_focal_ws_bytes(int64_t n) {
     if (n < 0 || n > ((int64_t)1 << 40)) return 0;
-    const size_t chunks = (size_t)lf_chunks(n);
-    return ((sizeof(double) * (chunks ? chunks : 1)) + 255) & ~size_t(255);
+    return p2w_ws_bytes([&](P2wArena& a) { lf_carve(a, n); });
 }
 
 extern "C" int32_t p2w_poly1_focal(const float* logits, const float* labels, const float* weight, int64_t weight_n, int64_t n,
@@ -216,9 +221,11 @@ extern "C" int32_t p2w_poly1_focal(const float* logits, const float* labels, con
     if (!(eps > 0.0 && eps < 0.5)) return P2W_EINVAL;
     if (alpha == alpha && !(alpha - alpha == 0.0)) return P2W_EINVAL;                                      // NaN (not set) or finite
     if (label_smoothing == label_smoothing && !(label_smoothing - label_smoothing == 0.0)) return P2W_EINVAL;
+    P2wArena arena(sum ? ws : nullptr);
+    double* partial = lf_carve(arena, n);                      // nullptr without `sum`
     if (sum) {
         P2W_CHECK_PTR(ws); P2W_CHECK_ALIGN16(ws);
-        if (ws_bytes < p2w_poly1_focal_ws_bytes(n)) return P2W_EWORKSPACE;
+        if (ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
     }
     const int wmode = weight == nullptr ? 0 : weight_n == 1 ? 1 : 2;
     if (n > 0) {
@@ -242,7 +249,6 @@ extern "C" int32_t p2w_poly1_focal(const float* logits, const float* labels, con
     P.ls_shift = P.has_ls ? (float)(0.5 * label_smoothing) : 0.0f;
     hipStream_t s = p2w_s(stream);
     const long long chunks = lf_chunks(n);
-    double* partial = sum ? static_cast<double*>(ws) : nullptr;
     if (chunks > 0 && (loss || dloss || sum)) {
         if (dloss) lf_launch<true>(wmode, (unsigned)chunks, s, logits, labels, weight, n, P, loss, dloss, partial);
         else lf_launch<false>(wmode, (unsigned)chunks, s, logits, labels, weight, n, P, loss, dloss, partial);

@@ -394,36 +394,32 @@ __global__ __launch_bounds__(PL_THREADS) void pl_weights_kernel(const double* __
         w[e] = pl_dist(xyz, (int)edges[2 * e], (int)edges[2 * e + 1]);
 }
 
-size_t pl_up(size_t v) { return (v + 255) & ~size_t(255); }
-
-struct GrowLayout { size_t st, f0, f1, total; };
-GrowLayout grow_layout(long long n) {
-    const size_t words = pl_up(sizeof(int) * (size_t)(n > 0 ? n : 1));
-    GrowLayout L;
-    L.st = 0;
-    L.f0 = 256;
-    L.f1 = L.f0 + words;
-    L.total = L.f1 + words;
-    return L;
+struct GrowWs { unsigned long long* st; int* fb[2]; };
+GrowWs grow_carve(P2wArena& a, long long n) {
+    const size_t nn = (size_t)(n > 0 ? n : 1);
+    GrowWs W;
+    W.st = a.take<unsigned long long>(ST_WORDS);
+    W.fb[0] = a.take<int>(nn);
+    W.fb[1] = a.take<int>(nn);
+    return W;
 }
 
-struct SsspLayout { size_t st, off, cursor, adj, w, dist, stamp, hop, f0, f1, temp, total; };
-SsspLayout sssp_layout(long long n, long long m) {
+struct SsspWs { unsigned long long* st; int *off, *cursor, *adj; double* w; unsigned long long* dist; int *stamp, *hop, *fb[2]; void* temp; };
+SsspWs sssp_carve(P2wArena& a, long long n, long long m) {
     const size_t nn = (size_t)(n > 0 ? n : 1), mm = (size_t)(m > 0 ? m : 1);
-    SsspLayout L;
-    L.st = 0;
-    L.off = 256;
-    L.cursor = L.off + pl_up(sizeof(int) * (nn + 1));
-    L.adj = L.cursor + pl_up(sizeof(int) * (nn + 1));
-    L.w = L.adj + pl_up(sizeof(int) * 2 * mm);
-    L.dist = L.w + pl_up(sizeof(double) * 2 * mm);
-    L.stamp = L.dist + pl_up(sizeof(double) * nn);
-    L.hop = L.stamp + pl_up(sizeof(int) * nn);
-    L.f0 = L.hop + pl_up(sizeof(int) * nn);
-    L.f1 = L.f0 + pl_up(sizeof(int) * nn);
-    L.temp = L.f1 + pl_up(sizeof(int) * nn);
-    L.total = L.temp + pl_up(xs_ws_bytes((long long)nn + 1));
-    return L;
+    SsspWs W;
+    W.st = a.take<unsigned long long>(ST_WORDS);
+    W.off = a.take<int>(nn + 1);
+    W.cursor = a.take<int>(nn + 1);
+    W.adj = a.take<int>(2 * mm);
+    W.w = a.take<double>(2 * mm);
+    W.dist = a.take<unsigned long long>(nn);
+    W.stamp = a.take<int>(nn);
+    W.hop = a.take<int>(nn);
+    W.fb[0] = a.take<int>(nn);
+    W.fb[1] = a.take<int>(nn);
+    W.temp = a.raw(xs_ws_bytes((long long)nn + 1));
+    return W;
 }
 
 int pl_grid_blocks(long long n) {                                         // grid of the frontier launches (grid-stride loops)
@@ -474,7 +470,7 @@ extern "C" int32_t p2w_knn_wide_f64(const double* xyz_sorted, const int32_t* ord
     return P2W_LAUNCH_STATUS();
 }
 
-extern "C" size_t p2w_pathlen_grow_ws_bytes(int64_t n) { return grow_layout(n).total; }
+extern "C" size_t p2w_pathlen_grow_ws_bytes(int64_t n) { return p2w_ws_bytes([&](P2wArena& a) { grow_carve(a, n); }); }
 
 extern "C" int32_t p2w_pathlen_grow(const double* xyz, const int32_t* nbr, int64_t n, int32_t k, int32_t base, int32_t kpairs,
                                     double nbrs_threshold, double nbrs_threshold_step, double graph_threshold, int32_t* step_out,
@@ -486,12 +482,12 @@ extern "C" int32_t p2w_pathlen_grow(const double* xyz, const int32_t* nbr, int64
     if (graph_threshold != graph_threshold) return P2W_EINVAL;
     P2W_CHECK_PTR(xyz); P2W_CHECK_PTR(nbr); P2W_CHECK_PTR(step_out); P2W_CHECK_PTR(edges_out); P2W_CHECK_PTR(info_out);
     P2W_CHECK_PTR(threshold_out); P2W_CHECK_PTR(ws); P2W_CHECK_ALIGN16(ws);
-    const GrowLayout L = grow_layout(n);
-    if (ws_bytes < L.total) return P2W_EWORKSPACE;
+    P2wArena arena(ws);
+    const GrowWs L = grow_carve(arena, n);
+    if (ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
     hipStream_t s = p2w_s(stream);
-    char* wb = static_cast<char*>(ws);
-    unsigned long long* st = reinterpret_cast<unsigned long long*>(wb + L.st);
-    int* const fb[2] = {reinterpret_cast<int*>(wb + L.f0), reinterpret_cast<int*>(wb + L.f1)};
+    unsigned long long* st = L.st;
+    int* const fb[2] = {L.fb[0], L.fb[1]};
     const int nn = (int)n, kp1 = kpairs + 1 < k ? kpairs + 1 : k, G = pl_grid_blocks(n);
     long long launches = 0, gaps = 0, raises = 0;
     unsigned long long h[ST_WORDS];
@@ -549,7 +545,7 @@ extern "C" int32_t p2w_pathlen_grow(const double* xyz, const int32_t* nbr, int64
     return 0;
 }
 
-extern "C" size_t p2w_pathlen_sssp_ws_bytes(int64_t n, int64_t n_edges) { return sssp_layout(n, n_edges).total; }
+extern "C" size_t p2w_pathlen_sssp_ws_bytes(int64_t n, int64_t n_edges) { return p2w_ws_bytes([&](P2wArena& a) { sssp_carve(a, n, n_edges); }); }
 
 extern "C" int32_t p2w_pathlen_sssp(const double* xyz, const int32_t* edges, int64_t n_edges, int64_t n, int32_t base, double* dist_out,
                                     int32_t* parent_out, int64_t* info_out, void* ws, size_t ws_bytes, p2w_stream_t stream) {
@@ -557,24 +553,19 @@ extern "C" int32_t p2w_pathlen_sssp(const double* xyz, const int32_t* edges, int
     if (n_edges < 0 || 2 * n_edges > (int64_t)0x7fffffff - 1) return P2W_EINVAL;
     P2W_CHECK_PTR(xyz); P2W_CHECK_PTR(dist_out); P2W_CHECK_PTR(info_out); P2W_CHECK_PTR(ws); P2W_CHECK_ALIGN16(ws);
     if (n_edges > 0) P2W_CHECK_PTR(edges);
-    const SsspLayout L = sssp_layout(n, n_edges);
-    if (ws_bytes < L.total) return P2W_EWORKSPACE;
+    P2wArena arena(ws);
+    const SsspWs L = sssp_carve(arena, n, n_edges);
+    if (ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
     hipStream_t s = p2w_s(stream);
-    char* wb = static_cast<char*>(ws);
-    unsigned long long* st = reinterpret_cast<unsigned long long*>(wb + L.st);
-    int* off = reinterpret_cast<int*>(wb + L.off);
-    int* cursor = reinterpret_cast<int*>(wb + L.cursor);
-    int* adj = reinterpret_cast<int*>(wb + L.adj);
-    double* w = reinterpret_cast<double*>(wb + L.w);
-    unsigned long long* dist = reinterpret_cast<unsigned long long*>(wb + L.dist);
-    int* stamp = reinterpret_cast<int*>(wb + L.stamp);
-    int* hop = reinterpret_cast<int*>(wb + L.hop);
-    int* const fb[2] = {reinterpret_cast<int*>(wb + L.f0), reinterpret_cast<int*>(wb + L.f1)};
+    unsigned long long *st = L.st, *dist = L.dist;
+    int *off = L.off, *cursor = L.cursor, *adj = L.adj, *stamp = L.stamp, *hop = L.hop;
+    double* w = L.w;
+    int* const fb[2] = {L.fb[0], L.fb[1]};
     const int nn = (int)n, G = pl_grid_blocks(n), GE = pl_grid_blocks(n_edges);
     hipError_t e;
     if ((e = hipMemsetAsync(off, 0, sizeof(int) * ((size_t)nn + 1), s)) != hipSuccess) return (int32_t)e;
     if (n_edges > 0) pl_degree_kernel<<<GE, PL_THREADS, 0, s>>>(edges, n_edges, off);
-    if ((e = xs_exclusive_scan(wb + L.temp, off, off, nn + 1, s)) != hipSuccess) return (int32_t)e;
+    if ((e = xs_exclusive_scan(L.temp, off, off, nn + 1, s)) != hipSuccess) return (int32_t)e;
     if ((e = hipMemcpyAsync(cursor, off, sizeof(int) * ((size_t)nn + 1), hipMemcpyDeviceToDevice, s)) != hipSuccess) return (int32_t)e;
     if (n_edges > 0) pl_csr_fill_kernel<<<GE, PL_THREADS, 0, s>>>(xyz, edges, n_edges, cursor, adj, w);
     pl_sssp_init_kernel<<<p2w_cdiv(n, PL_THREADS), PL_THREADS, 0, s>>>(dist, stamp, hop, nn);

@@ -45,7 +45,7 @@ inline int run_pieces(long long N, int rows) {
     return (int)(Z > RUN_SPLIT_MAX ? RUN_SPLIT_MAX : Z);
 }
 // the partial rows of run_sum (Z > 1 only; Z rows <= N / 256)
-inline size_t run_part_bytes(int Z, int rows, int panel) { return Z > 1 ? (size_t)Z * rows * panel * sizeof(float) : 0; }
+inline size_t run_part_floats(int Z, int rows, int panel) { return Z > 1 ? (size_t)Z * rows * panel : 0; }
 
 // One block per (row j, piece z of its run, panel).  The run [start[j], start[j + 1]) of the sorted slot list is cut into
 // gridDim.y = Z pieces at L z / Z; inside a piece the block's P = 256 / W row lanes (W = V-float lanes per row, a power of two
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void run_combine_kernel(const float* __restric
     gr_st<V>(&out[(size_t)j * ldo + c], acc);
 }
 
-// out[j, 0:F] = the sum of row j's run for j < rows (rows > 0); Z = run_pieces(N, rows), `part`: run_part_bytes(Z, rows, panel)
+// out[j, 0:F] = the sum of row j's run for j < rows (rows > 0); Z = run_pieces(N, rows), `part`: run_part_floats(Z, rows, panel) floats
 template <int V, class Term>
 inline void run_sum(const Term& term, int F, const int* start, const int* slot, int rows, int Z, float* part, float* out, int ldo,
                     hipStream_t s) {

@@ -241,51 +241,45 @@ __global__ __launch_bounds__(RS_BLOCK) void rs_finish_kernel(const unsigned long
     }
 }
 
-struct RsLayout { size_t ctl, hist, tsum, ktmp, vtmp, bytes; int nblk; };
-static inline void rs_layout(long long n_bound, RsLayout* L) {
-    auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
+struct RsWs { RsCtl* ctl; int *hist, *tsum; unsigned long long* ktmp; int* vtmp; int nblk; };
+static inline RsWs rs_carve(P2wArena& a, long long n_bound) {
     const long long n = n_bound > 0 ? n_bound : 1;
-    L->nblk = (int)((n + RS_TILE - 1) / RS_TILE);
-    size_t o = 0;
-    L->ctl = o; o += 256;
-    L->hist = o; o += up(sizeof(int) * (size_t)RS_RADIX * L->nblk);
-    L->tsum = o; o += up(sizeof(int) * (((size_t)RS_RADIX * L->nblk + 4095) / 4096));
-    L->ktmp = o; o += up(sizeof(unsigned long long) * (size_t)n);
-    L->vtmp = o; o += up(sizeof(int) * (size_t)n);
-    L->bytes = o;
+    RsWs W;
+    W.nblk = (int)((n + RS_TILE - 1) / RS_TILE);
+    W.ctl = a.take<RsCtl>(1);
+    W.hist = a.take<int>((size_t)RS_RADIX * W.nblk);
+    W.tsum = a.take<int>(((size_t)RS_RADIX * W.nblk + 4095) / 4096);
+    W.ktmp = a.take<unsigned long long>((size_t)n);
+    W.vtmp = a.take<int>((size_t)n);
+    return W;
 }
+static inline size_t rs_ws_bytes(long long n_bound) { return p2w_ws_bytes([&](P2wArena& a) { rs_carve(a, n_bound); }); }
 
 // Stable ascending sort of the first min(*n_dev, n_bound) (keys, values) pairs; vals_in == nullptr: values = 0..n-1 (an
-// argsort).  keys_in / vals_in are not modified; `ws` holds rs_layout(n_bound).bytes bytes.
+// argsort).  keys_in / vals_in are not modified; `ws` holds rs_ws_bytes(n_bound) bytes.
 static inline hipError_t rs_sort_pairs(void* ws, const unsigned long long* keys_in, unsigned long long* keys_out, const int* vals_in,
                                        int* vals_out, const int* n_dev, int n_bound, hipStream_t s) {
     if (n_bound <= 0) return hipSuccess;
-    RsLayout L;
-    rs_layout(n_bound, &L);
-    char* w = static_cast<char*>(ws);
-    auto* ctl = reinterpret_cast<RsCtl*>(w + L.ctl);
-    int* hist = reinterpret_cast<int*>(w + L.hist);
-    int* tsum = reinterpret_cast<int*>(w + L.tsum);
+    P2wArena arena(ws);
+    const RsWs L = rs_carve(arena, n_bound);
     const int hlen = RS_RADIX * L.nblk, ht = (hlen + 4095) / 4096;
-    auto* ktmp = reinterpret_cast<unsigned long long*>(w + L.ktmp);
-    int* vtmp = reinterpret_cast<int*>(w + L.vtmp);
-    hipError_t e = hipMemsetAsync(ctl, 0, sizeof(RsCtl), s);
+    hipError_t e = hipMemsetAsync(L.ctl, 0, sizeof(RsCtl), s);
     if (e != hipSuccess) return e;
     const int g1 = L.nblk < 1024 ? L.nblk : 1024;
-    rs_or_kernel<<<g1, RS_BLOCK, 0, s>>>(keys_in, n_dev, n_bound, ctl);
+    rs_or_kernel<<<g1, RS_BLOCK, 0, s>>>(keys_in, n_dev, n_bound, L.ctl);
     for (int p = 0; p < 8; ++p) {
-        rs_hist_kernel<<<L.nblk, RS_BLOCK, 0, s>>>(keys_in, keys_out, ktmp, n_dev, n_bound, p, ctl, L.nblk, hist);
+        rs_hist_kernel<<<L.nblk, RS_BLOCK, 0, s>>>(keys_in, keys_out, L.ktmp, n_dev, n_bound, p, L.ctl, L.nblk, L.hist);
         if (hlen <= RS_SCAN_ONE) {
-            rs_scan_kernel<<<1, 1024, 0, s>>>(hist, L.nblk, p, ctl);
+            rs_scan_kernel<<<1, 1024, 0, s>>>(L.hist, L.nblk, p, L.ctl);
         } else {
-            rs_scan_tile_kernel<<<ht, 1024, 0, s>>>(hist, hlen, p, ctl, tsum);
-            rs_scan_sums_kernel<<<1, 1024, 0, s>>>(tsum, ht, p, ctl);
-            rs_scan_add_kernel<<<(hlen + 255) / 256, 256, 0, s>>>(hist, hlen, p, ctl, tsum);
+            rs_scan_tile_kernel<<<ht, 1024, 0, s>>>(L.hist, hlen, p, L.ctl, L.tsum);
+            rs_scan_sums_kernel<<<1, 1024, 0, s>>>(L.tsum, ht, p, L.ctl);
+            rs_scan_add_kernel<<<(hlen + 255) / 256, 256, 0, s>>>(L.hist, hlen, p, L.ctl, L.tsum);
         }
-        rs_scatter_kernel<<<L.nblk, RS_BLOCK, 0, s>>>(keys_in, keys_out, ktmp, keys_out, ktmp, vals_in, vals_out, vtmp, vals_out, vtmp,
-                                                       n_dev, n_bound, p, ctl, L.nblk, hist);
+        rs_scatter_kernel<<<L.nblk, RS_BLOCK, 0, s>>>(keys_in, keys_out, L.ktmp, keys_out, L.ktmp, vals_in, vals_out, L.vtmp, vals_out, L.vtmp,
+                                                       n_dev, n_bound, p, L.ctl, L.nblk, L.hist);
     }
-    rs_finish_kernel<<<g1, RS_BLOCK, 0, s>>>(keys_in, keys_out, ktmp, vals_in, vals_out, vtmp, n_dev, n_bound, ctl);
+    rs_finish_kernel<<<g1, RS_BLOCK, 0, s>>>(keys_in, keys_out, L.ktmp, vals_in, vals_out, L.vtmp, n_dev, n_bound, L.ctl);
     return hipGetLastError();
 }
 
@@ -315,11 +309,18 @@ __global__ __launch_bounds__(256) void xs_add_kernel(int* __restrict__ out, int 
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i < n) out[i] += tsum[i >> 12];
 }
-static inline size_t xs_ws_bytes(long long n) { return (size_t)(((n > 0 ? n : 1) + 4095) / 4096) * sizeof(int) + 256; }
+// the tile sums, packed (the total is no multiple of 256), and 256 bytes of slack behind them
+static inline int* xs_carve(P2wArena& a, long long n) {
+    int* tsum = a.take<int>((size_t)(((n > 0 ? n : 1) + 4095) / 4096), alignof(int));
+    a.raw(256, 1);
+    return tsum;
+}
+static inline size_t xs_ws_bytes(long long n) { return p2w_ws_bytes([&](P2wArena& a) { xs_carve(a, n); }); }
 // out[i] = sum of in[0..i-1] for i < n (in place allowed: in == out); `ws`: xs_ws_bytes(n)
 static inline hipError_t xs_exclusive_scan(void* ws, const int* in, int* out, int n, hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    int* tsum = static_cast<int*>(ws);
+    P2wArena arena(ws);
+    int* tsum = xs_carve(arena, n);
     const int nt = (int)(((long long)n + 4095) / 4096);
     xs_tile_kernel<<<nt, 1024, 0, s>>>(in, out, n, tsum);
     if (nt > 1) {

@@ -25,7 +25,7 @@ from dataclasses import dataclass, field, fields
 import torch
 
 from . import _lib
-from ._lib import GEMM_RESIDUAL_H, PREC_F16X3, PREC_OF, SA_PACK8, SEARCH_BOX, SEARCH_Q_ROW_IN_W, SEARCH_X_INDEX_IN_W, Epilogue, check, lib, ptr
+from ._lib import GEMM_RESIDUAL_H, PREC_F16X3, PREC_OF, SA_PACK8, SEARCH_BOX, SEARCH_Q_ROW_IN_W, SEARCH_X_INDEX_IN_W, Epilogue, check, lib, ptr, ws_bytes
 
 BN_EPS = 1e-5
 SA_RES = (0.04, 0.08, 0.16)  # model.py:210-212
@@ -526,9 +526,7 @@ class Engine:
         self._call(name, lib().p2w_gemm, ptr(A), lda, ptr(lin.w), M, lin.N, lin.K, C.byref(ep), ptr(out), ldo)
 
     def _table_workspace(self, n, cells, device):
-        need = int(lib().p2w_voxel_sample_table_ws_bytes(n, cells))
-        if need == 0:
-            raise RuntimeError("p2w_voxel_sample_table_ws_bytes failed")
+        need = ws_bytes("voxel_sample_table", n, cells)
         if self._ws_t is None or self._ws_t.numel() < need or self._ws_t.device != device:
             self._ws_t = torch.empty(need, dtype=torch.uint8, device=device)
             # the sampler's between-calls state (p2w_voxel_sample_table_prepared): once per workspace, on the stream that will use it
@@ -536,9 +534,7 @@ class Engine:
         return self._ws_t
 
     def _workspace(self, n, device):
-        need = int(lib().p2w_voxel_sample_ws_bytes(n))
-        if need == 0:
-            raise RuntimeError("p2w_voxel_sample_ws_bytes failed (no usable HIP device?)")
+        need = ws_bytes("voxel_sample", n)
         if self._ws is None or self._ws.numel() < need or self._ws.device != device:
             self._ws = torch.empty(need, dtype=torch.uint8, device=device)
         return self._ws

@@ -30,7 +30,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from ._lib import check, lib, ptr, stream
+from ._lib import check, lib, ptr, stream, ws_bytes
 
 
 def _csr(batch, nb):
@@ -55,10 +55,7 @@ def _xyzr(pos):
 
 
 def _ws(n, device):
-    need = int(lib().p2w_voxel_sample_ws_bytes(max(n, 1)))
-    if need == 0:
-        raise RuntimeError("p2w_voxel_sample_ws_bytes failed")
-    return torch.empty(need, dtype=torch.uint8, device=device)
+    return torch.empty(ws_bytes("voxel_sample", max(n, 1)), dtype=torch.uint8, device=device)
 
 
 def voxel_grid(pos, size, batch=None):
@@ -227,10 +224,7 @@ class _KnnInterpolate(torch.autograd.Function):
         (n, F0), m = ctx.shape, rf.shape[0]
         g, F = _pad4(grad_out)
         grad_x = torch.empty((n, F), dtype=torch.float32, device=g.device)
-        need = int(lib().p2w_interp_bwd_ws_bytes(m, ctx.k, n))
-        if need == 0:
-            raise RuntimeError("p2w_interp_bwd_ws_bytes failed")
-        ws = torch.empty(need, dtype=torch.uint8, device=g.device)
+        ws = torch.empty(ws_bytes("interp_bwd", m, ctx.k, n), dtype=torch.uint8, device=g.device)
         check(lib().p2w_interp_bwd(ptr(g), F, F, ptr(rc), ptr(rf), ptr(nbr), ptr(deg), ctx.k, m, n, ptr(grad_x), F,
                                    ptr(ws), ws.numel(), stream()), "knn_interpolate backward")
         if F != F0:
@@ -289,10 +283,7 @@ class _EdgeLayer1(torch.autograd.Function):
         gP = torch.empty((n_src, C1), dtype=torch.float32, device=dev)
         gR = torch.empty(n_src, dtype=torch.float32, device=dev)
         gWg = torch.empty((4, C1), dtype=torch.float32, device=dev)
-        need = int(lib().p2w_edge_l1_bwd_ws_bytes(E, n_src, C1))
-        if need == 0:
-            raise RuntimeError("p2w_edge_l1_bwd_ws_bytes failed")
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = torch.empty(ws_bytes("edge_l1_bwd", E, n_src, C1), dtype=torch.uint8, device=dev)
         check(lib().p2w_edge_l1_bwd(ptr(g), C1, ptr(H1), C1, ptr(geo), ptr(src), ptr(Wg), n_src, E, C1, ptr(gP), C1, ptr(gR), ptr(gWg),
                                     ptr(ws), ws.numel(), stream()), "edge_layer1 backward")
         gpos = None
@@ -334,10 +325,7 @@ def _relu_bn_max_forward(zc, gamma, beta, csr, M, bn):
     arg = torch.empty((M, C2), dtype=torch.int32, device=dev)
     mean, invstd = (torch.empty(C2, dtype=torch.float32, device=dev) for _ in range(2))
     rm, rv = (t.detach().to(torch.float32).contiguous() for t in (bn.running_mean, bn.running_var))
-    need = int(lib().p2w_relu_bn_max_ws_bytes(E, M, C2))
-    if need == 0:
-        raise RuntimeError("p2w_relu_bn_max_ws_bytes failed")
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = torch.empty(ws_bytes("relu_bn_max", E, M, C2), dtype=torch.uint8, device=dev)
     check(lib().p2w_relu_bn_max(ptr(zc), C2, ptr(csr), ptr(gamma), ptr(beta), ptr(rm), ptr(rv), float(bn.momentum), float(bn.eps), E, M, C2,
                                 ptr(out), ptr(ext), ptr(arg), ptr(mean), ptr(invstd), ptr(ws), ws.numel(), stream()), "relu_bn_max")
     with torch.no_grad():
@@ -368,10 +356,7 @@ class _ReluBnMax(torch.autograd.Function):
         g = _f32c(grad_out)
         dz = torch.empty((E, C2), dtype=torch.float32, device=dev)
         dgamma, dbeta = (torch.empty(C2, dtype=torch.float32, device=dev) for _ in range(2))
-        need = int(lib().p2w_relu_bn_max_ws_bytes(E, M, C2))
-        if need == 0:
-            raise RuntimeError("p2w_relu_bn_max_ws_bytes failed")
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = torch.empty(ws_bytes("relu_bn_max", E, M, C2), dtype=torch.uint8, device=dev)
         check(lib().p2w_relu_bn_max_bwd(ptr(g), ptr(z), C2, ptr(csr), ptr(arg), ptr(ext), ptr(mean), ptr(invstd), ptr(gamma), E, M, C2,
                                         ptr(dz), C2, ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), stream()), "relu_bn_max backward")
         return dz.to(ctx.dtypes[0]), dgamma.to(ctx.dtypes[1]), dbeta.to(ctx.dtypes[2]), None, None, None
