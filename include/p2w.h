@@ -678,6 +678,62 @@ int32_t p2w_relu_bn_max_bwd(const float* g, const float* z, int32_t ldz, const i
                             const float* mean, const float* invstd, const float* gamma, int32_t E, int32_t M, int32_t C2, float* dz,
                             int32_t lddz, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, p2w_stream_t stream);
 
+/* ---- chains of depthwise convolution, training-mode BatchNorm1d and ReLU between two GEMMs (pointstowood_amd/ops.py: bn_chain) ---- */
+/* What the inverted residual block (model.py:46-85) runs between two of its 1x1 convolutions in training mode, on the pre-activation
+ * z[M, C] (pitch ldz).  A chain has L stages, 1 <= L <= P2W_BN_CHAIN_MAX; stage s = 1 .. L has the input u_{s-1}, u_0 = z:
+ *   v_s = fl(fl(dw_w u_{s-1}) + dw_b)                           the depthwise convolution with kernel size 1 (dw_w = dw_b = NULL: v_s = u_{s-1})
+ *   mean_s = (1 / M) sum v_s,  var_s = max((1 / M) sum v_s^2 - mean_s^2, 0),  invstd_s = 1 / sqrt(var_s + eps)
+ *            from the fp64 column sums of u_{s-1} and u_{s-1}^2 (mean_s = dw_w mean_u + dw_b, var_s = dw_w^2 var_u), fp64 arithmetic,
+ *            each result rounded to fp32 once; var is the biased batch variance
+ *   y_s = fl(fl(fl(fl(v_s - mean_s) invstd_s) gamma) + beta)    on the rounded mean and invstd, no fma
+ *   u_s = relu ? (y_s < 0 ? 0 : y_s) : y_s                      (a NaN stays a NaN and poisons its column, as in PyTorch)
+ *   running_mean = (1 - momentum) running_mean + momentum mean_s,  running_var likewise with var_s M / (M - 1)   (in place, fp64, rounded once)
+ * out (pitch ldo) = u_L, or with a residual res[M, C] (pitch ldr; NULL = none) out = max(u_L + res, 0).  mean and invstd are [L, C]
+ * (stage s at (s - 1) C).  2 L + 1 launches: per stage the fp64 column sums per work item of P2W_BN_CHAIN_ROWS consecutive rows (one
+ * lane per column walks them in ascending order, the stages before it recomputed in fp32 from z) and the items in ascending order with
+ * the statistics; then the chain on [M, C].  z is read L + 1 times, out written once, nothing else of that size exists.  No
+ * floating-point atomics: the bits depend on the inputs alone, not on the run, the grid or the access width.
+ * Access width: 16 bytes per lane when C and every pitch are multiples of 4 and z, res, out, mean, invstd and the stages' dw_w, dw_b,
+ * gamma, beta are 16-byte aligned, 4 bytes otherwise (same bits).  ws: 16-byte aligned (P2W_EALIGN), p2w_bn_chain_ws_size(M, C, L) bytes
+ * (0 = bad sizes; too small: P2W_EWORKSPACE; one size serves both directions).  2 <= M < 2^31 - 1 (one row has no variance), C >= 1,
+ * M C <= 2^38, 1 <= L <= P2W_BN_CHAIN_MAX, every pitch >= C, dw_w and dw_b both or neither, eps >= 0, 0 <= momentum <= 1 (P2W_EINVAL);
+ * every other pointer is required (P2W_ENULL).  `stages` is a HOST array read during the call.  A refused call launches nothing. */
+#define P2W_BN_CHAIN_MAX 3
+#define P2W_BN_CHAIN_ROWS 32
+typedef struct p2w_bn_stage {
+    const float* dw_w;        /* [C] depthwise weight and bias in front of the BatchNorm; both NULL = none */
+    const float* dw_b;
+    const float* gamma;       /* [C] BatchNorm's weight and bias */
+    const float* beta;
+    float* running_mean;      /* [C], updated in place by the forward; the backward does not look at them */
+    float* running_var;
+    double momentum;          /* the forward's; the backward does not look at them */
+    double eps;
+    int32_t relu;             /* != 0: ReLU behind the BatchNorm */
+} p2w_bn_stage;
+size_t p2w_bn_chain_ws_size(int32_t M, int32_t C, int32_t L);
+int32_t p2w_bn_chain(const float* z, int32_t ldz, const float* res, int32_t ldr, const p2w_bn_stage* stages, int32_t L, int32_t M,
+                     int32_t C, float* out, int32_t ldo, float* mean, float* invstd, void* ws, size_t ws_bytes, p2w_stream_t stream);
+/* Its backward, on z, the forward's mean and invstd, the stages' vectors and the gradient g[M, C] (pitch ldg) of out.  `out` (pitch ldo) is
+ * the forward's output where the chain had a residual and NULL where it had none: with it g = g [out > 0] first, and dres (pitch lddr;
+ * NULL = not wanted) = that g.  The forward is recomputed from z with the forward's code, so every ReLU mask is the forward's.  For
+ * s = L .. 1, with xhat_s = fl(fl(v_s - mean_s) invstd_s):
+ *   gy = relu_s ? g [u_s > 0] : g,   dbeta_s = sum gy,   dgamma_s = sum gy xhat_s
+ *            fp64 terms on the fp32 values, per work item in ascending row order, the items in ascending order, rounded to fp32 once;
+ *            k1 = dbeta_s / M and k2 = dgamma_s / M likewise
+ *   gv = fl(fl(fl(gy - k1) - fl(xhat_s k2)) fl(gamma invstd_s)),   g = fl(gv dw_w)                                    (fp32, no fma)
+ *   ddw_w_s = gamma invstd_s (sum gy u_{s-1} - (dbeta_s / M) sum u_{s-1} - (dgamma_s / M) sum xhat_s u_{s-1})   = sum gv u_{s-1}, in fp64 from
+ *            three more fp64 column sums taken beside the other two, rounded once; tiny against its terms (only eps keeps it from 0)
+ *   ddw_b_s = 0 exactly: BatchNorm removes a bias added in front of it (sum gv = 0 because sum xhat = 0)
+ * and dz (pitch lddz) = g.  dgamma, dbeta, ddw_w, ddw_b are [L, C], written, not added to; ddw_w and ddw_b are 0 for a stage without a
+ * depthwise convolution and may be NULL when no stage has one.  2 L + 1 launches; z and g are read L + 1 times, dz (and dres) written once;
+ * no other [M, C] tensor, no atomics.  Access width, ws and sizes as in the forward (g, z, out, dz, dres, mean, invstd, the stages' vectors
+ * and every pitch decide the width); dres needs out (P2W_EINVAL). */
+int32_t p2w_bn_chain_bwd(const float* g, int32_t ldg, const float* z, int32_t ldz, const float* out, int32_t ldo,
+                         const p2w_bn_stage* stages, int32_t L, const float* mean, const float* invstd, int32_t M, int32_t C, float* dz,
+                         int32_t lddz, float* dres, int32_t lddr, float* dgamma, float* dbeta, float* ddw_w, float* ddw_b, void* ws,
+                         size_t ws_bytes, p2w_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

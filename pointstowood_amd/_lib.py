@@ -22,6 +22,11 @@ class Epilogue(C.Structure):
                 ("interp", _vp), ("interp_rows", _i32)]
 
 
+class BnStage(C.Structure):                                     # include/p2w.h p2w_bn_stage
+    _fields_ = [("dw_w", _vp), ("dw_b", _vp), ("gamma", _vp), ("beta", _vp), ("running_mean", _vp), ("running_var", _vp),
+                ("momentum", C.c_double), ("eps", C.c_double), ("relu", _i32)]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/p2w.h
 SEARCH_X_INDEX_IN_W, SEARCH_Q_ROW_IN_W, SEARCH_BOX = 1, 2, 4   # include/p2w.h P2W_SEARCH_*
 PREC_F16X3, PREC_F16, PREC_BF16 = 0, 1, 2                      # include/p2w.h P2W_PREC_*
@@ -35,6 +40,7 @@ EVAL_CHUNK, EVAL_MAX_CLASSES = 4096, 8                                          
 LOSS_CHUNK = 4096                                                                                  # P2W_LOSS_CHUNK
 EDGE_CHUNK = 1024                                                                                  # P2W_EDGE_CHUNK
 BN_GROUP = 16                                                                                      # P2W_BN_GROUP
+BN_CHAIN_MAX, BN_CHAIN_ROWS = 3, 32                                                                # P2W_BN_CHAIN_*
 
 SIGNATURES = {
     "p2w_version": (_i32, []),
@@ -123,6 +129,10 @@ SIGNATURES = {
     "p2w_relu_bn_max": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                _vp]),
     "p2w_relu_bn_max_bwd": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "p2w_bn_chain_ws_size": (_sz, [_i32, _i32, _i32]),
+    "p2w_bn_chain": (_i32, [_vp, _i32, _vp, _i32, C.POINTER(BnStage), _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "p2w_bn_chain_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, C.POINTER(BnStage), _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp,
+                                _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

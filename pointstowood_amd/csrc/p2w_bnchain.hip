@@ -1,0 +1,455 @@
+// Everything between two GEMMs of the inverted residual block for training (model.py:46-85): a chain of up to P2W_BN_CHAIN_MAX
+// stages over the pre-activation Z [M, C], each an optional depthwise convolution with kernel size 1 (v = a u + b per column), a
+// training-mode BatchNorm1d and an optional ReLU, with an optional residual add and ReLU at the end.  Every stage is a map per
+// column once its two statistics are known, so the whole chain is computed from Z alone: one read of Z per BatchNorm for its
+// statistics (the earlier stages recomputed in fp32 on the way), one read and one write to apply the chain; the backward is one
+// read of Z and G per BatchNorm for its two column sums, BatchNorm's gradient through the batch statistics being a closed form in
+// them, and one pass that writes dZ.  Nothing of [M, C] size exists besides Z, the residual, the output and the gradients.
+//
+// Streaming kernels, bandwidth-bound: no LDS tiles, no MFMA.  A lane owns V adjacent columns (V = 4: 16-byte accesses when C, the
+// pitches and the pointers allow, V = 1: 4-byte accesses, the same bits) and walks the P2W_BN_CHAIN_ROWS consecutive rows of its
+// work item in ascending order; its column constants stay in registers.  Sums: fp64 partials per item, then the items in ascending
+// order (bc_reduce_kernel: the scheme of p2w_bnmax.hip's reduction, for K sums per column) - no floating-point atomics, the bits
+// depend on the inputs alone.  The forward recomputation inside the backward is the forward's own code on the forward's rounded
+// mean and invstd, so every ReLU mask is the forward's.
+#include "p2w_runsum.h"
+
+namespace {
+
+constexpr int BC_MAX = P2W_BN_CHAIN_MAX;
+constexpr int BC_R = P2W_BN_CHAIN_ROWS;
+constexpr int BC_KMAX = 5;                // sums per column of a backward stage with a depthwise convolution
+constexpr int BC_RED_U = 16;              // items per thread and batch of the reduction: 8 x 16 = 128 items per batch
+constexpr int BC_RED_BATCH = 8 * BC_RED_U;
+
+// what every kernel is given by value: the stages' column vectors ([C] each; a == nullptr: no depthwise), the statistics
+// ([L, C], written by the forward's reductions) and, in the backward, k1 = dbeta / M and k2 = dgamma / M per stage ([L, 2, C])
+struct BcParams {
+    const float* a[BC_MAX];
+    const float* b[BC_MAX];
+    const float* gamma[BC_MAX];
+    const float* beta[BC_MAX];
+    int relu[BC_MAX];
+    const float* mean;
+    const float* invstd;
+    const float* kq;
+};
+
+template <int V> struct BcCol { float a[V], b[V], mu[V], is[V], gm[V], bt[V]; };        // forward constants of one stage
+template <int V> struct BcGrad { float sc[V], k1[V], k2[V]; };                        // backward constants: sc = gamma invstd
+
+template <int V> __device__ __forceinline__ void bc_load(const BcParams& P, int t, int C, int c, BcCol<V>& k) {
+    if (P.a[t]) { gr_ld<V>(&P.a[t][c], k.a); gr_ld<V>(&P.b[t][c], k.b); }
+    else {
+#pragma unroll
+        for (int u = 0; u < V; ++u) { k.a[u] = 1.f; k.b[u] = 0.f; }                     // (1 u + 0 = u exactly)
+    }
+    gr_ld<V>(&P.mean[(size_t)t * C + c], k.mu);
+    gr_ld<V>(&P.invstd[(size_t)t * C + c], k.is);
+    gr_ld<V>(&P.gamma[t][c], k.gm);
+    gr_ld<V>(&P.beta[t][c], k.bt);
+}
+template <int V> __device__ __forceinline__ void bc_load_grad(const BcParams& P, int t, int C, int c, const BcCol<V>& k, BcGrad<V>& g) {
+    gr_ld<V>(&P.kq[((size_t)t * 2 + 0) * C + c], g.k1);
+    gr_ld<V>(&P.kq[((size_t)t * 2 + 1) * C + c], g.k2);
+#pragma unroll
+    for (int u = 0; u < V; ++u) g.sc[u] = k.gm[u] * k.is[u];
+}
+
+// one stage, fp32, every operation rounded on its own: v = a u + b, xhat = (v - mean) invstd, y = xhat gamma + beta,
+// u = relu ? (y < 0 ? 0 : y) : y   (a NaN stays a NaN, as torch.relu leaves it)
+template <int V> __device__ __forceinline__ void bc_stage(const BcCol<V>& k, bool relu, float (&x)[V], float (&xh)[V]) {
+#pragma unroll
+    for (int u = 0; u < V; ++u) {
+        const float v = k.a[u] * x[u] + k.b[u];
+        xh[u] = (v - k.mu[u]) * k.is[u];
+        const float y = xh[u] * k.gm[u] + k.bt[u];
+        x[u] = relu ? (y < 0.f ? 0.f : y) : y;
+    }
+}
+// the gradient through one stage: gy = relu ? g [u_out > 0] : g, gv = ((gy - k1) - xhat k2) sc, g = a gv
+template <int V>
+__device__ __forceinline__ void bc_stage_bwd(const BcCol<V>& k, const BcGrad<V>& q, bool relu, const float (&xh)[V], const float (&uo)[V],
+                                             float (&g)[V]) {
+#pragma unroll
+    for (int u = 0; u < V; ++u) {
+        const float gy = relu ? (uo[u] > 0.f ? g[u] : 0.f) : g[u];
+        g[u] = (((gy - q.k1[u]) - xh[u] * q.k2[u]) * q.sc[u]) * k.a[u];
+    }
+}
+
+#define BC_ITEM_PROLOGUE()                                                     \
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;           \
+    const int item = (int)(gid / q);                                           \
+    if (item >= items) return;                                                 \
+    const int c = (int)(gid % q) * V;                                          \
+    const int r0 = item * BC_R, r1 = min(M, r0 + BC_R)
+
+// Forward, statistics of stage S + 1 (S = the stages in front of it, recomputed): s1 = sum u_S, s2 = sum u_S^2 per item and column
+template <int V, int S>
+__global__ __launch_bounds__(256) void bc_stats_kernel(BcParams P, const float* __restrict__ z, int ldz, int M, int C, int q, int items,
+                                                       double* __restrict__ part) {
+    BC_ITEM_PROLOGUE();
+    BcCol<V> k[S > 0 ? S : 1];
+#pragma unroll
+    for (int t = 0; t < S; ++t) bc_load<V>(P, t, C, c, k[t]);
+    double s1[V], s2[V];
+#pragma unroll
+    for (int u = 0; u < V; ++u) { s1[u] = 0.0; s2[u] = 0.0; }
+#pragma unroll 4
+    for (int r = r0; r < r1; ++r) {
+        float x[V], xh[V];
+        gr_ld<V>(&z[(size_t)r * ldz + c], x);
+#pragma unroll
+        for (int t = 0; t < S; ++t) bc_stage<V>(k[t], P.relu[t] != 0, x, xh);
+#pragma unroll
+        for (int u = 0; u < V; ++u) {
+            const double xd = (double)x[u];
+            s1[u] = s1[u] + xd;
+            s2[u] = s2[u] + xd * xd;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < V; ++u) {
+        part[((size_t)item * 2 + 0) * C + c + u] = s1[u];
+        part[((size_t)item * 2 + 1) * C + c + u] = s2[u];
+    }
+}
+
+// Forward, last launch: out = u_L, or max(u_L + res, 0)
+template <int V, int L>
+__global__ __launch_bounds__(256) void bc_apply_kernel(BcParams P, const float* __restrict__ z, int ldz, const float* __restrict__ res, int ldr,
+                                                       int M, int C, int q, int items, float* __restrict__ out, int ldo) {
+    BC_ITEM_PROLOGUE();
+    BcCol<V> k[L];
+#pragma unroll
+    for (int t = 0; t < L; ++t) bc_load<V>(P, t, C, c, k[t]);
+#pragma unroll 4
+    for (int r = r0; r < r1; ++r) {
+        float x[V], xh[V];
+        gr_ld<V>(&z[(size_t)r * ldz + c], x);
+#pragma unroll
+        for (int t = 0; t < L; ++t) bc_stage<V>(k[t], P.relu[t] != 0, x, xh);
+        if (res) {
+            float rv[V];
+            gr_ld<V>(&res[(size_t)r * ldr + c], rv);
+#pragma unroll
+            for (int u = 0; u < V; ++u) { const float s = x[u] + rv[u]; x[u] = s < 0.f ? 0.f : s; }
+        }
+        gr_st<V>(&out[(size_t)r * ldo + c], x);
+    }
+}
+
+// the forward recomputed for the backward: xh[t] and uo[t] (the stage's output) of every stage, uin = the input of stage S (0-based)
+template <int V, int L>
+__device__ __forceinline__ void bc_replay(const BcParams& P, const BcCol<V> (&k)[L], int S, float (&x)[V], float (&xh)[L][V], float (&uo)[L][V],
+                                          float (&uin)[V]) {
+#pragma unroll
+    for (int t = 0; t < L; ++t) {
+        if (t == S) {
+#pragma unroll
+            for (int u = 0; u < V; ++u) uin[u] = x[u];
+        }
+        bc_stage<V>(k[t], P.relu[t] != 0, x, xh[t]);
+#pragma unroll
+        for (int u = 0; u < V; ++u) uo[t][u] = x[u];
+    }
+}
+
+// Backward, the sums of stage S (0-based; the stages above it are finished: their k1, k2 are in P.kq): per item and column
+//   s0 = sum gy, s1 = sum gy xhat_S, and with DW (the stage has a depthwise convolution, input u) s2 = sum gy u, s3 = sum u,
+//   s4 = sum xhat_S u - fp64 terms on the fp32 values.  `outp` (the forward's output) is given when the chain had a residual.
+template <int V, int L, int S, bool DW>
+__global__ __launch_bounds__(256) void bc_bwd_sums_kernel(BcParams P, const float* __restrict__ g, int ldg, const float* __restrict__ z, int ldz,
+                                                          const float* __restrict__ outp, int ldo, int M, int C, int q, int items,
+                                                          double* __restrict__ part) {
+    constexpr int K = DW ? BC_KMAX : 2;
+    BC_ITEM_PROLOGUE();
+    BcCol<V> k[L];
+    BcGrad<V> kg[L];
+#pragma unroll
+    for (int t = 0; t < L; ++t) {
+        bc_load<V>(P, t, C, c, k[t]);
+        if (t > S) bc_load_grad<V>(P, t, C, c, k[t], kg[t]);
+    }
+    double s[K][V];
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+#pragma unroll
+        for (int u = 0; u < V; ++u) s[j][u] = 0.0;
+#pragma unroll 2
+    for (int r = r0; r < r1; ++r) {
+        float x[V], xh[L][V], uo[L][V], uin[V], gg[V];
+        gr_ld<V>(&z[(size_t)r * ldz + c], x);
+        gr_ld<V>(&g[(size_t)r * ldg + c], gg);
+        bc_replay<V, L>(P, k, S, x, xh, uo, uin);
+        if (outp) {
+            float ov[V];
+            gr_ld<V>(&outp[(size_t)r * ldo + c], ov);
+#pragma unroll
+            for (int u = 0; u < V; ++u) gg[u] = ov[u] > 0.f ? gg[u] : 0.f;
+        }
+#pragma unroll
+        for (int t = L - 1; t > S; --t) bc_stage_bwd<V>(k[t], kg[t], P.relu[t] != 0, xh[t], uo[t], gg);
+#pragma unroll
+        for (int u = 0; u < V; ++u) {
+            const float gy = P.relu[S] ? (uo[S][u] > 0.f ? gg[u] : 0.f) : gg[u];
+            const double gd = (double)gy, xd = (double)xh[S][u];
+            s[0][u] = s[0][u] + gd;
+            s[1][u] = s[1][u] + gd * xd;
+            if constexpr (DW) {
+                const double ud = (double)uin[u];
+                s[2][u] = s[2][u] + gd * ud;
+                s[3][u] = s[3][u] + ud;
+                s[4][u] = s[4][u] + xd * ud;
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+#pragma unroll
+        for (int u = 0; u < V; ++u) part[((size_t)item * K + j) * C + c + u] = s[j][u];
+}
+
+// Backward, last launch: dz = the gradient through every stage, dres = g [out > 0]
+template <int V, int L>
+__global__ __launch_bounds__(256) void bc_dz_kernel(BcParams P, const float* __restrict__ g, int ldg, const float* __restrict__ z, int ldz,
+                                                    const float* __restrict__ outp, int ldo, int M, int C, int q, int items, float* __restrict__ dz,
+                                                    int lddz, float* __restrict__ dres, int lddr) {
+    BC_ITEM_PROLOGUE();
+    BcCol<V> k[L];
+    BcGrad<V> kg[L];
+#pragma unroll
+    for (int t = 0; t < L; ++t) { bc_load<V>(P, t, C, c, k[t]); bc_load_grad<V>(P, t, C, c, k[t], kg[t]); }
+#pragma unroll 2
+    for (int r = r0; r < r1; ++r) {
+        float x[V], xh[L][V], uo[L][V], uin[V], gg[V];
+        gr_ld<V>(&z[(size_t)r * ldz + c], x);
+        gr_ld<V>(&g[(size_t)r * ldg + c], gg);
+        bc_replay<V, L>(P, k, -1, x, xh, uo, uin);
+        if (outp) {
+            float ov[V];
+            gr_ld<V>(&outp[(size_t)r * ldo + c], ov);
+#pragma unroll
+            for (int u = 0; u < V; ++u) gg[u] = ov[u] > 0.f ? gg[u] : 0.f;
+            if (dres) gr_st<V>(&dres[(size_t)r * lddr + c], gg);
+        }
+#pragma unroll
+        for (int t = L - 1; t >= 0; --t) bc_stage_bwd<V>(k[t], kg[t], P.relu[t] != 0, xh[t], uo[t], gg);
+        gr_st<V>(&dz[(size_t)r * lddz + c], gg);
+    }
+}
+
+// what the reduction does with a column's K totals
+struct BcFinish {
+    int stats;                       // 1: forward statistics, 0: backward sums
+    const float* a; const float* b;  // the stage's depthwise vectors (nullptr: none)
+    const float* gamma; const float* invstd;                     // backward, K = 5
+    double momentum, eps;
+    float* o0; float* o1;            // mean, invstd | dgamma, dbeta
+    float* running_mean; float* running_var;
+    float* kq;                       // [2, C]: dbeta / M, dgamma / M
+    float* ddw_w; float* ddw_b;      // backward (nullptr: the caller wants none)
+};
+
+// The items in ascending order.  One block per CB = 32 / K columns; lane l of 32 = (sum kind l / CB, column l % CB), the block's 8
+// lane groups load BC_RED_BATCH items at a time into LDS (the next batch is in flight while this one is added), the first 32
+// threads add their chain's values in item order, and the first CB threads finish their column in fp64, rounding once:
+//   statistics: mean_u = s0 / M, var_u = max(s1 / M - mean_u^2, 0); mean = a mean_u + b, var = a^2 var_u with a depthwise in front;
+//               invstd = 1 / sqrt(var + eps); running_mean = (1 - m) running_mean + m mean, running_var likewise with var M / (M - 1)
+//   backward:   dbeta = s0, dgamma = s1, k1 = s0 / M, k2 = s1 / M,
+//               ddw_w = gamma invstd (s2 - (s0 / M) s3 - (s1 / M) s4)   (= sum gv u),   ddw_b = 0 (BatchNorm removes a bias in front of it)
+template <int K>
+__global__ __launch_bounds__(256) void bc_reduce_kernel(const double* __restrict__ part, int items, int C, int M, BcFinish F) {
+    constexpr int CB = 32 / K;
+    __shared__ double sm[BC_RED_BATCH][32];
+    __shared__ double tot[32];
+    const int l = threadIdx.x & 31, sub = threadIdx.x >> 5;
+    const int kind = l / CB, col = blockIdx.x * CB + l % CB;
+    const bool on = kind < K && col < C;
+    double v[BC_RED_U], acc = 0.0;
+#pragma unroll
+    for (int u = 0; u < BC_RED_U; ++u) {
+        const int it = u * 8 + sub;
+        v[u] = (on && it < items) ? part[((size_t)it * K + kind) * C + col] : 0.0;
+    }
+    for (int base = 0; base < items; base += BC_RED_BATCH) {
+#pragma unroll
+        for (int u = 0; u < BC_RED_U; ++u) sm[u * 8 + sub][l] = v[u];
+        __syncthreads();
+        if (base + BC_RED_BATCH < items) {
+#pragma unroll
+            for (int u = 0; u < BC_RED_U; ++u) {
+                const int it = base + BC_RED_BATCH + u * 8 + sub;
+                v[u] = (on && it < items) ? part[((size_t)it * K + kind) * C + col] : 0.0;
+            }
+        }
+        if (threadIdx.x < 32) {
+            const int n = min(BC_RED_BATCH, items - base);
+            for (int i = 0; i < n; ++i) acc = acc + sm[i][l];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 32) tot[l] = acc;
+    __syncthreads();
+    if (threadIdx.x >= CB || !on) return;
+    const double s0 = tot[l], s1 = tot[CB + l], n = (double)M;
+    if (F.stats) {
+        double mu = s0 / n;
+        double var = s1 / n - mu * mu;
+        var = var > 0.0 ? var : 0.0;
+        if (F.a) {
+            const double a = (double)F.a[col];
+            mu = a * mu + (double)F.b[col];
+            var = (a * a) * var;
+        }
+        F.o0[col] = (float)mu;
+        F.o1[col] = (float)(1.0 / sqrt(var + F.eps));
+        F.running_mean[col] = (float)((1.0 - F.momentum) * (double)F.running_mean[col] + F.momentum * mu);
+        F.running_var[col] = (float)((1.0 - F.momentum) * (double)F.running_var[col] + F.momentum * (var * n / (n - 1.0)));
+    } else {
+        F.o0[col] = (float)s1;       // dgamma
+        F.o1[col] = (float)s0;       // dbeta
+        F.kq[col] = (float)(s0 / n);
+        F.kq[C + col] = (float)(s1 / n);
+        if (F.ddw_w) {
+            double w = 0.0;
+            if constexpr (K == BC_KMAX) {
+                const double s2 = tot[2 * CB + l], s3 = tot[3 * CB + l], s4 = tot[4 * CB + l];
+                w = ((double)F.gamma[col] * (double)F.invstd[col]) * ((s2 - (s0 / n) * s3) - (s1 / n) * s4);
+            }
+            F.ddw_w[col] = (float)w;
+        }
+        if (F.ddw_b) F.ddw_b[col] = 0.f;
+    }
+}
+
+struct BcWs { double* part; float* kq; int items; };
+inline BcWs bc_carve(P2wArena& a, int M, int C, int L) {
+    BcWs W;
+    W.items = p2w_cdiv(M, BC_R);
+    W.part = a.take<double>((size_t)W.items * BC_KMAX * C);
+    W.kq = a.take<float>((size_t)L * 2 * C);
+    return W;
+}
+inline bool bc_sizes_ok(long long M, long long C, long long L) {
+    return M >= 2 && C >= 1 && L >= 1 && L <= BC_MAX && M < 0x7fffffffll && M * C <= (1ll << 38) && L * C < 0x7fffffffll;
+}
+
+// NULL and alignment of the stages' vectors; v4 is cleared where one of them is off 16 bytes
+inline int32_t bc_stages_ok(const p2w_bn_stage* st, int L, bool forward, bool& v4) {
+    for (int t = 0; t < L; ++t) {
+        if ((st[t].dw_w == nullptr) != (st[t].dw_b == nullptr)) return P2W_EINVAL;
+        P2W_CHECK_PTR(st[t].gamma); P2W_CHECK_PTR(st[t].beta);
+        if (forward) {
+            P2W_CHECK_PTR(st[t].running_mean); P2W_CHECK_PTR(st[t].running_var);
+            if (!(st[t].eps >= 0.0) || !(st[t].momentum >= 0.0 && st[t].momentum <= 1.0)) return P2W_EINVAL;
+        }
+        v4 = v4 && gr_al16(st[t].gamma) && gr_al16(st[t].beta) && gr_al16(st[t].dw_w) && gr_al16(st[t].dw_b);
+    }
+    return P2W_OK;
+}
+inline BcParams bc_params(const p2w_bn_stage* st, int L, const float* mean, const float* invstd, const float* kq) {
+    BcParams P{};
+    for (int t = 0; t < L; ++t) {
+        P.a[t] = st[t].dw_w; P.b[t] = st[t].dw_b; P.gamma[t] = st[t].gamma; P.beta[t] = st[t].beta; P.relu[t] = st[t].relu != 0;
+    }
+    P.mean = mean; P.invstd = invstd; P.kq = kq;
+    return P;
+}
+
+#define BC_GRID(items, q) (unsigned)(((long long)(items) * (q) + 255) / 256), 256, 0, s
+
+template <int V> void bc_forward(const BcParams& P, const p2w_bn_stage* st, int L, const float* z, int ldz, const float* res, int ldr, int M, int C,
+                                 float* out, int ldo, float* mean, float* invstd, const BcWs& W, hipStream_t s) {
+    const int q = C / V;
+    for (int t = 0; t < L; ++t) {
+        if (t == 0) bc_stats_kernel<V, 0><<<BC_GRID(W.items, q)>>>(P, z, ldz, M, C, q, W.items, W.part);
+        else if (t == 1) bc_stats_kernel<V, 1><<<BC_GRID(W.items, q)>>>(P, z, ldz, M, C, q, W.items, W.part);
+        else bc_stats_kernel<V, 2><<<BC_GRID(W.items, q)>>>(P, z, ldz, M, C, q, W.items, W.part);
+        BcFinish F{};
+        F.stats = 1; F.a = st[t].dw_w; F.b = st[t].dw_b; F.momentum = st[t].momentum; F.eps = st[t].eps;
+        F.o0 = mean + (size_t)t * C; F.o1 = invstd + (size_t)t * C; F.running_mean = st[t].running_mean; F.running_var = st[t].running_var;
+        bc_reduce_kernel<2><<<p2w_cdiv(C, 16), 256, 0, s>>>(W.part, W.items, C, M, F);
+    }
+    if (L == 1) bc_apply_kernel<V, 1><<<BC_GRID(W.items, q)>>>(P, z, ldz, res, ldr, M, C, q, W.items, out, ldo);
+    else if (L == 2) bc_apply_kernel<V, 2><<<BC_GRID(W.items, q)>>>(P, z, ldz, res, ldr, M, C, q, W.items, out, ldo);
+    else bc_apply_kernel<V, 3><<<BC_GRID(W.items, q)>>>(P, z, ldz, res, ldr, M, C, q, W.items, out, ldo);
+}
+
+template <int V, int L, int S> void bc_bwd_stage(const BcParams& P, const p2w_bn_stage* st, const float* g, int ldg, const float* z, int ldz,
+                                                 const float* outp, int ldo, const float* invstd, int M, int C, float* dgamma, float* dbeta,
+                                                 float* ddw_w, float* ddw_b, const BcWs& W, hipStream_t s) {
+    const int q = C / V;
+    const bool dw = st[S].dw_w != nullptr;
+    if (dw) bc_bwd_sums_kernel<V, L, S, true><<<BC_GRID(W.items, q)>>>(P, g, ldg, z, ldz, outp, ldo, M, C, q, W.items, W.part);
+    else bc_bwd_sums_kernel<V, L, S, false><<<BC_GRID(W.items, q)>>>(P, g, ldg, z, ldz, outp, ldo, M, C, q, W.items, W.part);
+    BcFinish F{};
+    F.a = st[S].dw_w; F.b = st[S].dw_b; F.gamma = st[S].gamma; F.invstd = invstd + (size_t)S * C;
+    F.o0 = dgamma + (size_t)S * C; F.o1 = dbeta + (size_t)S * C; F.kq = W.kq + (size_t)S * 2 * C;
+    F.ddw_w = ddw_w ? ddw_w + (size_t)S * C : nullptr; F.ddw_b = ddw_b ? ddw_b + (size_t)S * C : nullptr;
+    if (dw) bc_reduce_kernel<BC_KMAX><<<p2w_cdiv(C, 32 / BC_KMAX), 256, 0, s>>>(W.part, W.items, C, M, F);
+    else bc_reduce_kernel<2><<<p2w_cdiv(C, 16), 256, 0, s>>>(W.part, W.items, C, M, F);
+}
+
+template <int V, int L> void bc_backward(const BcParams& P, const p2w_bn_stage* st, const float* g, int ldg, const float* z, int ldz, const float* outp,
+                                         int ldo, const float* invstd, int M, int C, float* dz, int lddz, float* dres, int lddr, float* dgamma,
+                                         float* dbeta, float* ddw_w, float* ddw_b, const BcWs& W, hipStream_t s) {
+    if constexpr (L >= 3) bc_bwd_stage<V, L, 2>(P, st, g, ldg, z, ldz, outp, ldo, invstd, M, C, dgamma, dbeta, ddw_w, ddw_b, W, s);
+    if constexpr (L >= 2) bc_bwd_stage<V, L, 1>(P, st, g, ldg, z, ldz, outp, ldo, invstd, M, C, dgamma, dbeta, ddw_w, ddw_b, W, s);
+    bc_bwd_stage<V, L, 0>(P, st, g, ldg, z, ldz, outp, ldo, invstd, M, C, dgamma, dbeta, ddw_w, ddw_b, W, s);
+    bc_dz_kernel<V, L><<<BC_GRID(W.items, C / V)>>>(P, g, ldg, z, ldz, outp, ldo, M, C, C / V, W.items, dz, lddz, dres, lddr);
+}
+
+}  // namespace
+
+extern "C" size_t p2w_bn_chain_ws_size(int32_t M, int32_t C, int32_t L) {
+    if (!bc_sizes_ok(M, C, L)) return 0;
+    return p2w_ws_bytes([&](P2wArena& a) { bc_carve(a, M, C, L); });
+}
+
+extern "C" int32_t p2w_bn_chain(const float* z, int32_t ldz, const float* res, int32_t ldr, const p2w_bn_stage* stages, int32_t L, int32_t M,
+                                int32_t C, float* out, int32_t ldo, float* mean, float* invstd, void* ws, size_t ws_bytes, p2w_stream_t stream) {
+    if (!bc_sizes_ok(M, C, L) || ldz < C || ldo < C || (res && ldr < C)) return P2W_EINVAL;
+    P2W_CHECK_PTR(z); P2W_CHECK_PTR(stages); P2W_CHECK_PTR(out); P2W_CHECK_PTR(mean); P2W_CHECK_PTR(invstd); P2W_CHECK_PTR(ws);
+    bool v4 = !(C & 3) && !(ldz & 3) && !(ldo & 3) && (!res || !(ldr & 3)) && gr_al16(z) && gr_al16(res) && gr_al16(out) && gr_al16(mean) &&
+              gr_al16(invstd);
+    const int32_t bad = bc_stages_ok(stages, L, true, v4);
+    if (bad != P2W_OK) return bad;
+    P2W_CHECK_ALIGN16(ws);
+    P2wArena arena(ws);
+    const BcWs W = bc_carve(arena, M, C, L);
+    if (ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
+    const BcParams P = bc_params(stages, L, mean, invstd, nullptr);
+    hipStream_t s = p2w_s(stream);
+    if (v4) bc_forward<4>(P, stages, L, z, ldz, res, ldr, M, C, out, ldo, mean, invstd, W, s);
+    else bc_forward<1>(P, stages, L, z, ldz, res, ldr, M, C, out, ldo, mean, invstd, W, s);
+    return P2W_LAUNCH_STATUS();
+}
+
+extern "C" int32_t p2w_bn_chain_bwd(const float* g, int32_t ldg, const float* z, int32_t ldz, const float* out, int32_t ldo,
+                                    const p2w_bn_stage* stages, int32_t L, const float* mean, const float* invstd, int32_t M, int32_t C, float* dz,
+                                    int32_t lddz, float* dres, int32_t lddr, float* dgamma, float* dbeta, float* ddw_w, float* ddw_b, void* ws,
+                                    size_t ws_bytes, p2w_stream_t stream) {
+    if (!bc_sizes_ok(M, C, L) || ldg < C || ldz < C || lddz < C || (out && ldo < C) || (dres && (lddr < C || !out))) return P2W_EINVAL;
+    P2W_CHECK_PTR(g); P2W_CHECK_PTR(z); P2W_CHECK_PTR(stages); P2W_CHECK_PTR(mean); P2W_CHECK_PTR(invstd); P2W_CHECK_PTR(dz);
+    P2W_CHECK_PTR(dgamma); P2W_CHECK_PTR(dbeta); P2W_CHECK_PTR(ws);
+    bool v4 = !(C & 3) && !(ldg & 3) && !(ldz & 3) && !(lddz & 3) && (!out || !(ldo & 3)) && (!dres || !(lddr & 3)) && gr_al16(g) && gr_al16(z) &&
+              gr_al16(out) && gr_al16(mean) && gr_al16(invstd) && gr_al16(dz) && gr_al16(dres);
+    const int32_t bad = bc_stages_ok(stages, L, false, v4);
+    if (bad != P2W_OK) return bad;
+    for (int t = 0; t < L; ++t)
+        if (stages[t].dw_w && (!ddw_w || !ddw_b)) return P2W_ENULL;
+    P2W_CHECK_ALIGN16(ws);
+    P2wArena arena(ws);
+    const BcWs W = bc_carve(arena, M, C, L);
+    if (ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
+    v4 = v4 && gr_al16(W.kq);
+    const BcParams P = bc_params(stages, L, mean, invstd, W.kq);
+    hipStream_t s = p2w_s(stream);
+#define BC_BWD(V, LL) bc_backward<V, LL>(P, stages, g, ldg, z, ldz, out, ldo, invstd, M, C, dz, lddz, dres, lddr, dgamma, dbeta, ddw_w, ddw_b, W, s)
+    if (v4) { if (L == 1) BC_BWD(4, 1); else if (L == 2) BC_BWD(4, 2); else BC_BWD(4, 3); }
+    else { if (L == 1) BC_BWD(1, 1); else if (L == 2) BC_BWD(1, 2); else BC_BWD(1, 3); }
+#undef BC_BWD
+    return P2W_LAUNCH_STATUS();
+}

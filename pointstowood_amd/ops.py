@@ -23,7 +23,9 @@ positions, batch vectors and indices get none.  A tied maximum sends its whole g
 trains through ``edge_layer1`` (``csrc/p2w_edge.hip``: the hoisted layer 1 of the edge MLP with a deterministic backward) and
 ``scatter_max``, or, with ``fused_bn_max``, through ``relu_bn_max`` (``csrc/p2w_bnmax.hip``: ReLU, training-mode BatchNorm1d and the
 segment max in one forward and one backward kernel, differentiable with respect to its input and BatchNorm's weight and bias); its
-fused eval-mode kernel and ``Net.forward`` stay inference-only.
+fused eval-mode kernel and ``Net.forward`` stay inference-only.  ``InvertedResidualBlock`` (``model.py:46-85``) trains through
+``bn_chain`` (``csrc/p2w_bnchain.hip``): everything between two of its 1x1 convolutions - depthwise convolution, training-mode
+BatchNorm1d, ReLU, up to three times, and the residual add - computed from the GEMM's output alone in both directions.
 """
 from __future__ import annotations
 
@@ -592,3 +594,224 @@ class PointNetConv(MessagePassing):
         if self.global_nn is not None:
             out = self.global_nn(out)
         return out
+
+
+# --------------------------------------------------------------------------- chains of BatchNorms between two GEMMs
+def _chain_stage_array(meta, vec, running):
+    """The host array of ``p2w_bn_stage`` for ``meta`` = [(bn, relu, has_dw)] over the flat fp32 vectors ``vec`` (per stage gamma, beta
+    and, with a depthwise convolution, its weight and bias); ``running`` = [(running_mean, running_var)] or None (backward)."""
+    arr, i = (_lib.BnStage * len(meta))(), 0
+    for t, (bn, relu, has_dw) in enumerate(meta):
+        gamma, beta = vec[i], vec[i + 1]
+        dw_w, dw_b = (vec[i + 2], vec[i + 3]) if has_dw else (None, None)
+        i += 4 if has_dw else 2
+        rm, rv = running[t] if running is not None else (None, None)
+        arr[t] = _lib.BnStage(ptr(dw_w), ptr(dw_b), ptr(gamma), ptr(beta), ptr(rm), ptr(rv), float(bn.momentum), float(bn.eps), int(bool(relu)))
+    return arr
+
+
+def _chain_ws(M, C, L, dev):
+    need = int(lib().p2w_bn_chain_ws_size(M, C, L))
+    if need == 0:
+        raise RuntimeError(f"p2w_bn_chain_ws_size({M}, {C}, {L}) failed")
+    return torch.empty(need, dtype=torch.uint8, device=dev)
+
+
+def _bn_chain_forward(zc, rc, meta, vec):
+    """(out, mean, invstd) of ``p2w_bn_chain`` on fp32, contiguous inputs; every bn's running statistics move in place."""
+    (M, C), L, dev = zc.shape, len(meta), zc.device
+    out = torch.empty((M, C), dtype=torch.float32, device=dev)
+    mean, invstd = (torch.empty((L, C), dtype=torch.float32, device=dev) for _ in range(2))
+    running = [tuple(t.detach().to(torch.float32).contiguous() for t in (bn.running_mean, bn.running_var)) for bn, _, _ in meta]
+    ws = _chain_ws(M, C, L, dev)
+    check(lib().p2w_bn_chain(ptr(zc), C, ptr(rc), C, _chain_stage_array(meta, vec, running), L, M, C, ptr(out), C, ptr(mean), ptr(invstd),
+                             ptr(ws), ws.numel(), stream()), "bn_chain")
+    with torch.no_grad():
+        for (bn, _, _), (rm, rv) in zip(meta, running):
+            for mine, theirs in ((rm, bn.running_mean), (rv, bn.running_var)):
+                if mine.data_ptr() != theirs.data_ptr():
+                    theirs.copy_(mine)
+    return out, mean, invstd
+
+
+class _BnChain(torch.autograd.Function):
+    """``p2w_bn_chain`` forward, ``p2w_bn_chain_bwd`` backward: gradients with respect to z, the residual, every BatchNorm's weight and
+    bias and every depthwise weight and bias.  Saved for backward: z, the output where the chain has a residual (its sign is the last
+    ReLU's mask; the residual itself is not needed), and [L, C] / [C] tensors - no other [M, C] tensor.  The gradient with respect
+    to a depthwise bias is exactly zero: BatchNorm subtracts the column mean, which removes any bias added in front of it."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, z, residual, meta, *params):          # (meta holds modules and flags, no tensors: custom_fwd passes it through)
+        zc = _f32c(z)
+        rc = None if residual is None else _f32c(residual)
+        vec = [_f32c(p.reshape(-1)) for p in params]
+        out, mean, invstd = _bn_chain_forward(zc, rc, meta, vec)
+        ctx.save_for_backward(zc, mean, invstd, *vec, *([out] if rc is not None else []))
+        ctx.meta, ctx.has_res = meta, rc is not None
+        ctx.like = [(t.dtype, t.shape) for t in (z, *params)] + ([(residual.dtype, residual.shape)] if rc is not None else [])
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_out):
+        saved = ctx.saved_tensors
+        z, mean, invstd = saved[:3]
+        meta, n_vec = ctx.meta, sum(4 if m[2] else 2 for m in ctx.meta)
+        vec, out = saved[3:3 + n_vec], (saved[3 + n_vec] if ctx.has_res else None)
+        (M, C), L, dev = z.shape, len(meta), z.device
+        g = _f32c(grad_out)
+        dz = torch.empty((M, C), dtype=torch.float32, device=dev)
+        dres = torch.empty((M, C), dtype=torch.float32, device=dev) if ctx.has_res and ctx.needs_input_grad[1] else None
+        dgamma, dbeta = (torch.empty((L, C), dtype=torch.float32, device=dev) for _ in range(2))
+        any_dw = any(m[2] for m in meta)
+        ddw_w, ddw_b = (torch.empty((L, C), dtype=torch.float32, device=dev) for _ in range(2)) if any_dw else (None, None)
+        ws = _chain_ws(M, C, L, dev)
+        check(lib().p2w_bn_chain_bwd(ptr(g), C, ptr(z), C, ptr(out), C, _chain_stage_array(meta, vec, None), L, ptr(mean), ptr(invstd), M, C,
+                                     ptr(dz), C, ptr(dres), C, ptr(dgamma), ptr(dbeta), ptr(ddw_w), ptr(ddw_b), ptr(ws), ws.numel(), stream()),
+              "bn_chain backward")
+        grads = []
+        for t, (_, _, has_dw) in enumerate(meta):
+            grads += [dgamma[t], dbeta[t]] + ([ddw_w[t], ddw_b[t]] if has_dw else [])
+        like = ctx.like
+        grads = [gr.to(dt).reshape(shape) for gr, (dt, shape) in zip(grads, like[1:1 + n_vec])]
+        return (dz.to(like[0][0]), None if dres is None else dres.to(like[-1][0]), None, *grads)
+
+
+def _chain_normalise(stages, C, who="bn_chain"):
+    meta = []
+    for st in stages:
+        bn, relu, dw = st if len(st) == 3 else (*st, None)
+        if not isinstance(bn, torch.nn.BatchNorm1d):
+            raise TypeError(f"{who}: every stage is (BatchNorm1d, relu) or (BatchNorm1d, relu, depthwise Conv1d or None)")
+        if not bn.affine or not bn.track_running_stats or bn.momentum is None:
+            raise NotImplementedError(f"{who} supports BatchNorm1d(affine=True, track_running_stats=True, momentum=<float>) as the reference builds it")
+        if bn.num_features != C:
+            raise RuntimeError(f"{who}: z [M, C] with C = num_features of every BatchNorm1d")
+        if dw is not None:
+            if not (isinstance(dw, torch.nn.Conv1d) and dw.in_channels == dw.out_channels == dw.groups == C and dw.kernel_size == (1,)
+                    and dw.stride == (1,) and dw.padding == (0,)):
+                raise TypeError(f"{who}: a depthwise convolution is Conv1d(C, C, 1, groups=C)")
+            if dw.bias is None:
+                raise NotImplementedError(f"{who} supports a depthwise Conv1d with a bias as the reference builds it")
+        meta.append((bn, bool(relu), dw))
+    return meta
+
+
+def bn_chain(z, stages, residual=None):
+    """Everything the reference's ``InvertedResidualBlock`` (``model.py:46-85``) runs between two of its 1x1 convolutions, on the
+    pre-activation ``z`` [M, C] in rows: for every stage of ``stages``, in order, an optional depthwise ``Conv1d(C, C, 1, groups=C)``
+    (``w[c] * x + b[c]``), a ``torch.nn.BatchNorm1d`` and an optional ReLU; then, with ``residual`` [M, C], ``relu(x + residual)``.
+    ``stages`` is a list of ``(bn, relu)`` or ``(bn, relu, depthwise_conv)``, one to three of them.
+
+    Training mode (``csrc/p2w_bnchain.hip``): once a BatchNorm's two statistics are known every stage is a map per column, so the chain
+    is computed from ``z`` alone - one read of ``z`` per BatchNorm for its fp64 column sums (the stages in front of it recomputed on
+    the way; the statistics of ``w * u + b`` follow from those of ``u``), one read and one write to apply the chain; the backward reads
+    ``z`` and the output's gradient once per BatchNorm for its two column sums and once more to write the gradient with respect to
+    ``z``.  Saved for backward: ``z``, the output where there is a residual, and [L, C] tensors; no intermediate activation.
+    Gradients go to ``z``, ``residual``, every ``bn.weight`` and ``bn.bias`` and every depthwise weight and bias in their dtypes.  The
+    gradient with respect to a depthwise bias is exactly zero - BatchNorm removes a bias added in front of it - and is returned as
+    zeros; the one with respect to a depthwise weight is tiny against its terms (only ``eps`` keeps it from zero) and is taken from
+    fp64 sums.  Running statistics (unbiased variance) and ``num_batches_tracked`` of every stage update as PyTorch's.  No
+    floating-point atomics: the same bits on every run.  Computes in fp32 under autocast.  Under ``no_grad`` the forward runs, the
+    statistics move and nothing is saved.
+
+    Every ``bn`` must be in the same mode.  In eval mode this is the plain composition on the running statistics.  ``affine=False``,
+    ``track_running_stats=False``, ``momentum=None`` and a depthwise convolution without a bias raise ``NotImplementedError``; fewer
+    than two rows in training mode raise PyTorch's ``ValueError``."""
+    _lib.require_cuda(z, residual)
+    if z.dim() != 2:
+        raise RuntimeError("bn_chain: z [M, C]")
+    if not 1 <= len(stages) <= _lib.BN_CHAIN_MAX:
+        raise RuntimeError(f"bn_chain: one to {_lib.BN_CHAIN_MAX} stages")
+    meta = _chain_normalise(stages, z.shape[1])
+    if residual is not None and residual.shape != z.shape:
+        raise RuntimeError("bn_chain: residual has z's shape")
+    if len({bn.training for bn, _, _ in meta}) != 1:
+        raise RuntimeError("bn_chain: every BatchNorm1d must be in the same mode")
+    if not meta[0][0].training:
+        x = z
+        for bn, relu, dw in meta:
+            if dw is not None:
+                x = x * dw.weight.reshape(-1) + dw.bias
+            x = bn(x)
+            if relu:
+                x = torch.relu(x)
+        return x if residual is None else torch.relu(x + residual)
+    if z.shape[0] < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {z.size()}")
+    for bn, _, _ in meta:
+        if bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
+    params = []
+    for bn, _, dw in meta:
+        params += [bn.weight, bn.bias] + ([dw.weight, dw.bias] if dw is not None else [])
+    flags = [(bn, relu, dw is not None) for bn, relu, dw in meta]
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (z, residual, *params)):
+        return _BnChain.apply(z, residual, flags, *params)
+    return _bn_chain_forward(_f32c(z), None if residual is None else _f32c(residual), flags, [_f32c(p.reshape(-1)) for p in params])[0]
+
+
+class _DepthwiseSeparable(torch.nn.Module):
+    """Holds the four submodules of the reference's ``DepthwiseSeparableConv1d(C, C, kernel_size=1)`` under its names."""
+
+    def __init__(self, channels):
+        super().__init__()
+        self.depthwise_conv = torch.nn.Conv1d(channels, channels, kernel_size=1, groups=channels)
+        self.depthwise_bn = torch.nn.BatchNorm1d(channels)
+        self.pointwise_conv = torch.nn.Conv1d(channels, channels, kernel_size=1)
+        self.pointwise_bn = torch.nn.BatchNorm1d(channels)
+
+
+def _rows_conv(conv, x):
+    """A ``Conv1d(kernel_size=1)`` on rows: a Linear over the channels."""
+    return torch.nn.functional.linear(x, conv.weight[:, :, 0], conv.bias)
+
+
+class InvertedResidualBlock(torch.nn.Module):
+    """Drop-in for the reference's ``InvertedResidualBlock`` (``model.py:46-85``): the same constructor, the same submodule tree and
+    therefore the same ``state_dict`` keys (``expand.0/1``, ``conv.0.*``, ``conv.1``, ``conv.3.*``, ``conv.4``, ``project.0/1``,
+    ``shortcut.0/1`` where ``in_channels != out_channels``), the same ``forward(x)`` on ``x`` [M, in_channels] in rows - without the
+    transposed [1, C, M] view.
+
+    Training mode: the four 1x1 convolutions are ``F.linear`` on ``weight[:, :, 0]``, and everything between them - eight training-mode
+    BatchNorms (nine with a shortcut), seven ReLUs, two depthwise convolutions, the residual add - is four ``bn_chain`` calls (five with a shortcut), so no
+    activation besides the four GEMM outputs is kept for the backward.  Eval mode is the plain composition statement by statement."""
+
+    def __init__(self, in_channels, out_channels, expansion_factor=4):
+        super().__init__()
+        from torch.nn import BatchNorm1d, Conv1d, ReLU, Sequential
+        self.expansion_factor = expansion_factor
+        e = in_channels * expansion_factor
+        self.expand = Sequential(Conv1d(in_channels, e, kernel_size=1), BatchNorm1d(e), ReLU())
+        self.conv = Sequential(_DepthwiseSeparable(e), BatchNorm1d(e), ReLU(), _DepthwiseSeparable(e), BatchNorm1d(e))
+        self.project = Sequential(Conv1d(e, out_channels, kernel_size=1), BatchNorm1d(out_channels))
+        self.shortcut = (Sequential(Conv1d(in_channels, out_channels, kernel_size=1), BatchNorm1d(out_channels))
+                         if in_channels != out_channels else Sequential())
+
+    def forward(self, x):
+        if x.dim() != 2 or x.shape[1] != self.expand[0].in_channels:
+            raise RuntimeError("InvertedResidualBlock: x [M, in_channels]")
+        if not self.training:
+            return self._forward_plain(x)
+        d0, d3 = self.conv[0], self.conv[3]
+        h = bn_chain(_rows_conv(self.expand[0], x), [(self.expand[1], True), (d0.depthwise_bn, True, d0.depthwise_conv)])
+        h = bn_chain(_rows_conv(d0.pointwise_conv, h), [(d0.pointwise_bn, True), (self.conv[1], True), (d3.depthwise_bn, True, d3.depthwise_conv)])
+        h = bn_chain(_rows_conv(d3.pointwise_conv, h), [(d3.pointwise_bn, True), (self.conv[4], False)])
+        res = bn_chain(_rows_conv(self.shortcut[0], x), [(self.shortcut[1], False)]) if len(self.shortcut) else x
+        return bn_chain(_rows_conv(self.project[0], h), [(self.project[1], False)], residual=res)
+
+    def _forward_plain(self, x):
+        relu = torch.relu
+        out = relu(self.expand[1](_rows_conv(self.expand[0], x)))
+        for i in (0, 3):
+            d = self.conv[i]
+            out = out * d.depthwise_conv.weight[:, 0, 0] + d.depthwise_conv.bias
+            out = relu(d.depthwise_bn(out))
+            out = relu(d.pointwise_bn(_rows_conv(d.pointwise_conv, out)))
+            if i == 0:
+                out = relu(self.conv[1](out))
+        out = self.conv[4](out)
+        out = self.project[1](_rows_conv(self.project[0], out))
+        res = self.shortcut[1](_rows_conv(self.shortcut[0], x)) if len(self.shortcut) else x
+        return relu(out + res)

@@ -28,6 +28,7 @@ static std::vector<Region> g_regions;
 #include "../pointstowood_amd/csrc/p2w_loss.hip"
 #include "../pointstowood_amd/csrc/p2w_edge.hip"
 #include "../pointstowood_amd/csrc/p2w_bnmax.hip"
+#include "../pointstowood_amd/csrc/p2w_bnchain.hip"
 
 static int g_fail = 0, g_runs = 0;
 
@@ -84,6 +85,8 @@ int main() {
             for (int C : {1, 32, 33, 67}) {
                 check("eb_carve", n, rows, C, [&](P2wArena& a) { eb_carve(a, i, rows, C); });
                 if (n > 0) check("bm_carve", n, C, 0, [&](P2wArena& a) { bm_carve(a, i, C); });
+                if (n > 1 && rows == 1)
+                    for (int L = 1; L <= P2W_BN_CHAIN_MAX; ++L) check("bc_carve", n, C, L, [&](P2wArena& a) { bc_carve(a, i, C, L); });
             }
         }
     }
