@@ -734,6 +734,60 @@ int32_t p2w_bn_chain_bwd(const float* g, int32_t ldg, const float* z, int32_t ld
                          int32_t lddz, float* dres, int32_t lddr, float* dgamma, float* dbeta, float* ddw_w, float* ddw_b, void* ws,
                          size_t ws_bytes, p2w_stream_t stream);
 
+/* ---- ReLU in front of one training-mode BatchNorm1d on rows (pointstowood_amd/ops.py: relu_bn) ---- */
+/* The tail of the feature-propagation MLP (model.py:198-202: Linear, ReLU, BatchNorm1d) on the pre-activation z[M, C] (pitch ldz):
+ * out = BN(relu(z)).  By definition the one-stage p2w_bn_chain (no depthwise convolution, no ReLU behind the BatchNorm, no residual) on
+ *   u = z < 0 ? 0 : z                                           (a NaN stays a NaN and poisons its column)
+ * computed as z is loaded - u is never stored.  Formulas, rounding points, the fp64 column sums per P2W_BN_CHAIN_ROWS consecutive rows in
+ * ascending order, the work items in ascending order and the running-statistics update are that chain's (the same device code), so out,
+ * mean, invstd [C] and running_* equal p2w_bn_chain on a materialised relu(z) bit for bit.  Three launches; z is read twice, out
+ * (pitch ldo) written once, no other [M, C] tensor, no atomics.  Access width, alignment, sizes and status codes as p2w_bn_chain with
+ * L = 1; ws: p2w_relu_bn_ws_size(M, C) bytes (= p2w_bn_chain_ws_size(M, C, 1); 0 = bad sizes; one size serves both directions).
+ * A refused call launches nothing. */
+size_t p2w_relu_bn_ws_size(int32_t M, int32_t C);
+int32_t p2w_relu_bn(const float* z, int32_t ldz, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                    double momentum, double eps, int32_t M, int32_t C, float* out, int32_t ldo, float* mean, float* invstd, void* ws,
+                    size_t ws_bytes, p2w_stream_t stream);
+/* Its backward, on z, the forward's mean and invstd, gamma and the gradient g[M, C] (pitch ldg) of out: that chain's backward with
+ *   xhat = fl(fl(u - mean) invstd),   dbeta = sum g,   dgamma = sum g xhat,   k1 = dbeta / M,   k2 = dgamma / M        (fp64 sums as there)
+ *   gv = fl(fl(fl(g - k1) - fl(xhat k2)) fl(gamma invstd)),      dz = z > 0 ? gv : 0                                    (pitch lddz)
+ * dgamma, dbeta [C] are written, not added to.  Three launches; z and g are read twice, dz written once; no other [M, C] tensor, no
+ * atomics.  Width, ws and sizes as in the forward. */
+int32_t p2w_relu_bn_bwd(const float* g, int32_t ldg, const float* z, int32_t ldz, const float* gamma, const float* mean,
+                        const float* invstd, int32_t M, int32_t C, float* dz, int32_t lddz, float* dgamma, float* dbeta, void* ws,
+                        size_t ws_bytes, p2w_stream_t stream);
+
+/* ---- layer 0 of the feature-propagation module for training (pointstowood_amd/ops.py: interp_add_relu, FPModule) ---- */
+/* knn_interpolate is linear in the coarse features and its weights sum to 1, so layer 0 of FPModule's MLP (model.py:142-153) on
+ * [interp(xc) | x_skip] is interp(Pc) + S with Pc[n_c, C] (pitch ldp) = xc W0[:, :Fc]^T on the coarse rows and S[m, C] (pitch lds) =
+ * x_skip W0[:, Fc:]^T + b0 on the fine rows, both the caller's GEMMs.  For fine row q < m and column c < C, in fp32 without fma:
+ *   t = num / den    p2w_interp_concat's arithmetic on Pc: w_s = 1 / max(d2, 1e-16), d2 = (dx dx + dy dy) + dz dz,
+ *                    num = ((0 + Pc[n_0, c] w_0) + Pc[n_1, c] w_1) + ... and den = ((0 + w_0) + w_1) + ... in slot order over
+ *                    s < min(deg[q], kw), a literal division; t = 0 where deg[q] <= 0
+ *   h = fl(t + S[q, c]),    H[q, c] = h < 0 ? 0 : h                              (pitch ldh; a NaN stays a NaN)
+ * xyzr_c[n_c, 4], xyzr_f[m, 4] = x, y, z, (unused); nbr[m, kw], deg[m] as the searches write them.  nbr[q, s] for s < deg[q] lies in
+ * [0, n_c): the caller's contract (the kernel clamps it into the range, and takes deg as 0 where n_c = 0, so no index is followed out
+ * of bounds).  One launch (one wave per row, 16-byte accesses, two 256-column chunks' loads in flight for rows of up to four
+ * neighbours), no workspace, no atomics; S is read once, H written once, the rows of Pc are gathered.  Neither the interpolated
+ * [m, C] tensor nor the [m, Fc + Fs] concatenation is formed.
+ * 1 <= kw <= P2W_MAX_K_WIDE, m kw < 2^31, m, n_c >= 0, C >= 4, C and every pitch multiples of 4, pitches >= C (P2W_EINVAL); every
+ * tensor 16-byte aligned (P2W_EALIGN); m = 0: P2W_OK without a launch. */
+int32_t p2w_interp_add_relu(const float* Pc, int32_t ldp, const float* S, int32_t lds, const float* xyzr_c, const float* xyzr_f,
+                            const int32_t* nbr, const int32_t* deg, int32_t kw, int32_t m, int32_t n_c, int32_t C, float* H, int32_t ldh,
+                            p2w_stream_t stream);
+/* Its backward, on the forward's output H and the gradient g[m, C] (pitch ldg) of H:
+ *   dS[q, c]  = H[q, c] > 0 ? g[q, c] : 0                                        (pitch ldds; one pass: reads g and H, writes dS)
+ *   dPc[j, :] = sum over the slots (q, s), s < deg[q], nbr[q, s] == j, of a(q, s) dS[q, :]      (pitch lddp)
+ * dPc is p2w_interp_bwd of dS - that entry point itself, on this workspace: the stable sort, the run sums in ascending slot order, the
+ * tree fixed by the sizes, the same bits; a coarse row nobody references gets zeros.  Every element of dS [m, C] and dPc [n_c, C] is
+ * written: the caller clears nothing.  No floating-point atomics.  Sizes and alignment as in the forward (g, H, dS, dPc, xyzr_*, ws:
+ * P2W_EALIGN); ws: p2w_interp_add_relu_bwd_ws_size(m, kw, n_c) bytes (0 = bad sizes; too small: P2W_EWORKSPACE).  A refused call
+ * launches nothing. */
+size_t p2w_interp_add_relu_bwd_ws_size(int32_t m, int32_t kw, int32_t n_c);
+int32_t p2w_interp_add_relu_bwd(const float* g, int32_t ldg, const float* H, int32_t ldh, const float* xyzr_c, const float* xyzr_f,
+                                const int32_t* nbr, const int32_t* deg, int32_t kw, int32_t m, int32_t n_c, int32_t C, float* dS,
+                                int32_t ldds, float* dPc, int32_t lddp, void* ws, size_t ws_bytes, p2w_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

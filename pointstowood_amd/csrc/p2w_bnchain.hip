@@ -12,6 +12,10 @@
 // order (bc_reduce_kernel: the scheme of p2w_bnmax.hip's reduction, for K sums per column) - no floating-point atomics, the bits
 // depend on the inputs alone.  The forward recomputation inside the backward is the forward's own code on the forward's rounded
 // mean and invstd, so every ReLU mask is the forward's.
+//
+// p2w_relu_bn (the tail of the feature-propagation MLP, model.py:198-202: Linear, ReLU, BatchNorm1d) is the one-stage chain on
+// u = (z < 0 ? 0 : z): the same kernels with the compile-time switch PRE, which clamps z as it is loaded and masks dz with z > 0.
+// PRE exists for one stage only; every other instantiation is PRE = false and compiles to the code it was.
 #include "p2w_runsum.h"
 
 namespace {
@@ -78,6 +82,12 @@ __device__ __forceinline__ void bc_stage_bwd(const BcCol<V>& k, const BcGrad<V>&
     }
 }
 
+// the leading ReLU of p2w_relu_bn: u = z < 0 ? 0 : z (a NaN stays a NaN)
+template <int V> __device__ __forceinline__ void bc_pre(float (&x)[V]) {
+#pragma unroll
+    for (int u = 0; u < V; ++u) x[u] = x[u] < 0.f ? 0.f : x[u];
+}
+
 #define BC_ITEM_PROLOGUE()                                                     \
     const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;           \
     const int item = (int)(gid / q);                                           \
@@ -86,7 +96,7 @@ __device__ __forceinline__ void bc_stage_bwd(const BcCol<V>& k, const BcGrad<V>&
     const int r0 = item * BC_R, r1 = min(M, r0 + BC_R)
 
 // Forward, statistics of stage S + 1 (S = the stages in front of it, recomputed): s1 = sum u_S, s2 = sum u_S^2 per item and column
-template <int V, int S>
+template <int V, int S, bool PRE = false>
 __global__ __launch_bounds__(256) void bc_stats_kernel(BcParams P, const float* __restrict__ z, int ldz, int M, int C, int q, int items,
                                                        double* __restrict__ part) {
     BC_ITEM_PROLOGUE();
@@ -100,6 +110,7 @@ __global__ __launch_bounds__(256) void bc_stats_kernel(BcParams P, const float* 
     for (int r = r0; r < r1; ++r) {
         float x[V], xh[V];
         gr_ld<V>(&z[(size_t)r * ldz + c], x);
+        if constexpr (PRE) bc_pre<V>(x);
 #pragma unroll
         for (int t = 0; t < S; ++t) bc_stage<V>(k[t], P.relu[t] != 0, x, xh);
 #pragma unroll
@@ -117,7 +128,7 @@ __global__ __launch_bounds__(256) void bc_stats_kernel(BcParams P, const float* 
 }
 
 // Forward, last launch: out = u_L, or max(u_L + res, 0)
-template <int V, int L>
+template <int V, int L, bool PRE = false>
 __global__ __launch_bounds__(256) void bc_apply_kernel(BcParams P, const float* __restrict__ z, int ldz, const float* __restrict__ res, int ldr,
                                                        int M, int C, int q, int items, float* __restrict__ out, int ldo) {
     BC_ITEM_PROLOGUE();
@@ -128,6 +139,7 @@ __global__ __launch_bounds__(256) void bc_apply_kernel(BcParams P, const float* 
     for (int r = r0; r < r1; ++r) {
         float x[V], xh[V];
         gr_ld<V>(&z[(size_t)r * ldz + c], x);
+        if constexpr (PRE) bc_pre<V>(x);
 #pragma unroll
         for (int t = 0; t < L; ++t) bc_stage<V>(k[t], P.relu[t] != 0, x, xh);
         if (res) {
@@ -159,7 +171,7 @@ __device__ __forceinline__ void bc_replay(const BcParams& P, const BcCol<V> (&k)
 // Backward, the sums of stage S (0-based; the stages above it are finished: their k1, k2 are in P.kq): per item and column
 //   s0 = sum gy, s1 = sum gy xhat_S, and with DW (the stage has a depthwise convolution, input u) s2 = sum gy u, s3 = sum u,
 //   s4 = sum xhat_S u - fp64 terms on the fp32 values.  `outp` (the forward's output) is given when the chain had a residual.
-template <int V, int L, int S, bool DW>
+template <int V, int L, int S, bool DW, bool PRE = false>
 __global__ __launch_bounds__(256) void bc_bwd_sums_kernel(BcParams P, const float* __restrict__ g, int ldg, const float* __restrict__ z, int ldz,
                                                           const float* __restrict__ outp, int ldo, int M, int C, int q, int items,
                                                           double* __restrict__ part) {
@@ -182,6 +194,7 @@ __global__ __launch_bounds__(256) void bc_bwd_sums_kernel(BcParams P, const floa
         float x[V], xh[L][V], uo[L][V], uin[V], gg[V];
         gr_ld<V>(&z[(size_t)r * ldz + c], x);
         gr_ld<V>(&g[(size_t)r * ldg + c], gg);
+        if constexpr (PRE) bc_pre<V>(x);
         bc_replay<V, L>(P, k, S, x, xh, uo, uin);
         if (outp) {
             float ov[V];
@@ -212,7 +225,7 @@ __global__ __launch_bounds__(256) void bc_bwd_sums_kernel(BcParams P, const floa
 }
 
 // Backward, last launch: dz = the gradient through every stage, dres = g [out > 0]
-template <int V, int L>
+template <int V, int L, bool PRE = false>
 __global__ __launch_bounds__(256) void bc_dz_kernel(BcParams P, const float* __restrict__ g, int ldg, const float* __restrict__ z, int ldz,
                                                     const float* __restrict__ outp, int ldo, int M, int C, int q, int items, float* __restrict__ dz,
                                                     int lddz, float* __restrict__ dres, int lddr) {
@@ -226,6 +239,12 @@ __global__ __launch_bounds__(256) void bc_dz_kernel(BcParams P, const float* __r
         float x[V], xh[L][V], uo[L][V], uin[V], gg[V];
         gr_ld<V>(&z[(size_t)r * ldz + c], x);
         gr_ld<V>(&g[(size_t)r * ldg + c], gg);
+        [[maybe_unused]] float zin[V];
+        if constexpr (PRE) {
+#pragma unroll
+            for (int u = 0; u < V; ++u) zin[u] = x[u];
+            bc_pre<V>(x);
+        }
         bc_replay<V, L>(P, k, -1, x, xh, uo, uin);
         if (outp) {
             float ov[V];
@@ -236,6 +255,10 @@ __global__ __launch_bounds__(256) void bc_dz_kernel(BcParams P, const float* __r
         }
 #pragma unroll
         for (int t = L - 1; t >= 0; --t) bc_stage_bwd<V>(k[t], kg[t], P.relu[t] != 0, xh[t], uo[t], gg);
+        if constexpr (PRE) {
+#pragma unroll
+            for (int u = 0; u < V; ++u) gg[u] = zin[u] > 0.f ? gg[u] : 0.f;
+        }
         gr_st<V>(&dz[(size_t)r * lddz + c], gg);
     }
 }
@@ -360,11 +383,11 @@ inline BcParams bc_params(const p2w_bn_stage* st, int L, const float* mean, cons
 
 #define BC_GRID(items, q) (unsigned)(((long long)(items) * (q) + 255) / 256), 256, 0, s
 
-template <int V> void bc_forward(const BcParams& P, const p2w_bn_stage* st, int L, const float* z, int ldz, const float* res, int ldr, int M, int C,
+template <int V, bool PRE = false> void bc_forward(const BcParams& P, const p2w_bn_stage* st, int L, const float* z, int ldz, const float* res, int ldr, int M, int C,
                                  float* out, int ldo, float* mean, float* invstd, const BcWs& W, hipStream_t s) {
     const int q = C / V;
     for (int t = 0; t < L; ++t) {
-        if (t == 0) bc_stats_kernel<V, 0><<<BC_GRID(W.items, q)>>>(P, z, ldz, M, C, q, W.items, W.part);
+        if (t == 0) bc_stats_kernel<V, 0, PRE><<<BC_GRID(W.items, q)>>>(P, z, ldz, M, C, q, W.items, W.part);
         else if (t == 1) bc_stats_kernel<V, 1><<<BC_GRID(W.items, q)>>>(P, z, ldz, M, C, q, W.items, W.part);
         else bc_stats_kernel<V, 2><<<BC_GRID(W.items, q)>>>(P, z, ldz, M, C, q, W.items, W.part);
         BcFinish F{};
@@ -372,17 +395,18 @@ template <int V> void bc_forward(const BcParams& P, const p2w_bn_stage* st, int 
         F.o0 = mean + (size_t)t * C; F.o1 = invstd + (size_t)t * C; F.running_mean = st[t].running_mean; F.running_var = st[t].running_var;
         bc_reduce_kernel<2><<<p2w_cdiv(C, 16), 256, 0, s>>>(W.part, W.items, C, M, F);
     }
-    if (L == 1) bc_apply_kernel<V, 1><<<BC_GRID(W.items, q)>>>(P, z, ldz, res, ldr, M, C, q, W.items, out, ldo);
+    if (L == 1) bc_apply_kernel<V, 1, PRE><<<BC_GRID(W.items, q)>>>(P, z, ldz, res, ldr, M, C, q, W.items, out, ldo);
     else if (L == 2) bc_apply_kernel<V, 2><<<BC_GRID(W.items, q)>>>(P, z, ldz, res, ldr, M, C, q, W.items, out, ldo);
     else bc_apply_kernel<V, 3><<<BC_GRID(W.items, q)>>>(P, z, ldz, res, ldr, M, C, q, W.items, out, ldo);
 }
 
-template <int V, int L, int S> void bc_bwd_stage(const BcParams& P, const p2w_bn_stage* st, const float* g, int ldg, const float* z, int ldz,
+template <int V, int L, int S, bool PRE = false> void bc_bwd_stage(const BcParams& P, const p2w_bn_stage* st, const float* g, int ldg, const float* z, int ldz,
                                                  const float* outp, int ldo, const float* invstd, int M, int C, float* dgamma, float* dbeta,
                                                  float* ddw_w, float* ddw_b, const BcWs& W, hipStream_t s) {
     const int q = C / V;
     const bool dw = st[S].dw_w != nullptr;
-    if (dw) bc_bwd_sums_kernel<V, L, S, true><<<BC_GRID(W.items, q)>>>(P, g, ldg, z, ldz, outp, ldo, M, C, q, W.items, W.part);
+    if constexpr (PRE) bc_bwd_sums_kernel<V, L, S, false, true><<<BC_GRID(W.items, q)>>>(P, g, ldg, z, ldz, outp, ldo, M, C, q, W.items, W.part);
+    else if (dw) bc_bwd_sums_kernel<V, L, S, true><<<BC_GRID(W.items, q)>>>(P, g, ldg, z, ldz, outp, ldo, M, C, q, W.items, W.part);
     else bc_bwd_sums_kernel<V, L, S, false><<<BC_GRID(W.items, q)>>>(P, g, ldg, z, ldz, outp, ldo, M, C, q, W.items, W.part);
     BcFinish F{};
     F.a = st[S].dw_w; F.b = st[S].dw_b; F.gamma = st[S].gamma; F.invstd = invstd + (size_t)S * C;
@@ -392,24 +416,18 @@ template <int V, int L, int S> void bc_bwd_stage(const BcParams& P, const p2w_bn
     else bc_reduce_kernel<2><<<p2w_cdiv(C, 16), 256, 0, s>>>(W.part, W.items, C, M, F);
 }
 
-template <int V, int L> void bc_backward(const BcParams& P, const p2w_bn_stage* st, const float* g, int ldg, const float* z, int ldz, const float* outp,
+template <int V, int L, bool PRE = false> void bc_backward(const BcParams& P, const p2w_bn_stage* st, const float* g, int ldg, const float* z, int ldz, const float* outp,
                                          int ldo, const float* invstd, int M, int C, float* dz, int lddz, float* dres, int lddr, float* dgamma,
                                          float* dbeta, float* ddw_w, float* ddw_b, const BcWs& W, hipStream_t s) {
     if constexpr (L >= 3) bc_bwd_stage<V, L, 2>(P, st, g, ldg, z, ldz, outp, ldo, invstd, M, C, dgamma, dbeta, ddw_w, ddw_b, W, s);
     if constexpr (L >= 2) bc_bwd_stage<V, L, 1>(P, st, g, ldg, z, ldz, outp, ldo, invstd, M, C, dgamma, dbeta, ddw_w, ddw_b, W, s);
-    bc_bwd_stage<V, L, 0>(P, st, g, ldg, z, ldz, outp, ldo, invstd, M, C, dgamma, dbeta, ddw_w, ddw_b, W, s);
-    bc_dz_kernel<V, L><<<BC_GRID(W.items, C / V)>>>(P, g, ldg, z, ldz, outp, ldo, M, C, C / V, W.items, dz, lddz, dres, lddr);
+    bc_bwd_stage<V, L, 0, PRE>(P, st, g, ldg, z, ldz, outp, ldo, invstd, M, C, dgamma, dbeta, ddw_w, ddw_b, W, s);
+    bc_dz_kernel<V, L, PRE><<<BC_GRID(W.items, C / V)>>>(P, g, ldg, z, ldz, outp, ldo, M, C, C / V, W.items, dz, lddz, dres, lddr);
 }
 
-}  // namespace
-
-extern "C" size_t p2w_bn_chain_ws_size(int32_t M, int32_t C, int32_t L) {
-    if (!bc_sizes_ok(M, C, L)) return 0;
-    return p2w_ws_bytes([&](P2wArena& a) { bc_carve(a, M, C, L); });
-}
-
-extern "C" int32_t p2w_bn_chain(const float* z, int32_t ldz, const float* res, int32_t ldr, const p2w_bn_stage* stages, int32_t L, int32_t M,
-                                int32_t C, float* out, int32_t ldo, float* mean, float* invstd, void* ws, size_t ws_bytes, p2w_stream_t stream) {
+// the two entry points' bodies; pre (p2w_relu_bn) is a chain of one stage without a depthwise convolution and without a residual
+int32_t bc_chain_forward(bool pre, const float* z, int32_t ldz, const float* res, int32_t ldr, const p2w_bn_stage* stages, int32_t L, int32_t M,
+                         int32_t C, float* out, int32_t ldo, float* mean, float* invstd, void* ws, size_t ws_bytes, p2w_stream_t stream) {
     if (!bc_sizes_ok(M, C, L) || ldz < C || ldo < C || (res && ldr < C)) return P2W_EINVAL;
     P2W_CHECK_PTR(z); P2W_CHECK_PTR(stages); P2W_CHECK_PTR(out); P2W_CHECK_PTR(mean); P2W_CHECK_PTR(invstd); P2W_CHECK_PTR(ws);
     bool v4 = !(C & 3) && !(ldz & 3) && !(ldo & 3) && (!res || !(ldr & 3)) && gr_al16(z) && gr_al16(res) && gr_al16(out) && gr_al16(mean) &&
@@ -422,15 +440,20 @@ extern "C" int32_t p2w_bn_chain(const float* z, int32_t ldz, const float* res, i
     if (ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
     const BcParams P = bc_params(stages, L, mean, invstd, nullptr);
     hipStream_t s = p2w_s(stream);
-    if (v4) bc_forward<4>(P, stages, L, z, ldz, res, ldr, M, C, out, ldo, mean, invstd, W, s);
-    else bc_forward<1>(P, stages, L, z, ldz, res, ldr, M, C, out, ldo, mean, invstd, W, s);
+    if (pre) {
+        if (v4) bc_forward<4, true>(P, stages, 1, z, ldz, nullptr, 0, M, C, out, ldo, mean, invstd, W, s);
+        else bc_forward<1, true>(P, stages, 1, z, ldz, nullptr, 0, M, C, out, ldo, mean, invstd, W, s);
+    } else {
+        if (v4) bc_forward<4>(P, stages, L, z, ldz, res, ldr, M, C, out, ldo, mean, invstd, W, s);
+        else bc_forward<1>(P, stages, L, z, ldz, res, ldr, M, C, out, ldo, mean, invstd, W, s);
+    }
     return P2W_LAUNCH_STATUS();
 }
 
-extern "C" int32_t p2w_bn_chain_bwd(const float* g, int32_t ldg, const float* z, int32_t ldz, const float* out, int32_t ldo,
-                                    const p2w_bn_stage* stages, int32_t L, const float* mean, const float* invstd, int32_t M, int32_t C, float* dz,
-                                    int32_t lddz, float* dres, int32_t lddr, float* dgamma, float* dbeta, float* ddw_w, float* ddw_b, void* ws,
-                                    size_t ws_bytes, p2w_stream_t stream) {
+int32_t bc_chain_backward(bool pre, const float* g, int32_t ldg, const float* z, int32_t ldz, const float* out, int32_t ldo,
+                          const p2w_bn_stage* stages, int32_t L, const float* mean, const float* invstd, int32_t M, int32_t C, float* dz,
+                          int32_t lddz, float* dres, int32_t lddr, float* dgamma, float* dbeta, float* ddw_w, float* ddw_b, void* ws,
+                          size_t ws_bytes, p2w_stream_t stream) {
     if (!bc_sizes_ok(M, C, L) || ldg < C || ldz < C || lddz < C || (out && ldo < C) || (dres && (lddr < C || !out))) return P2W_EINVAL;
     P2W_CHECK_PTR(g); P2W_CHECK_PTR(z); P2W_CHECK_PTR(stages); P2W_CHECK_PTR(mean); P2W_CHECK_PTR(invstd); P2W_CHECK_PTR(dz);
     P2W_CHECK_PTR(dgamma); P2W_CHECK_PTR(dbeta); P2W_CHECK_PTR(ws);
@@ -447,9 +470,49 @@ extern "C" int32_t p2w_bn_chain_bwd(const float* g, int32_t ldg, const float* z,
     v4 = v4 && gr_al16(W.kq);
     const BcParams P = bc_params(stages, L, mean, invstd, W.kq);
     hipStream_t s = p2w_s(stream);
-#define BC_BWD(V, LL) bc_backward<V, LL>(P, stages, g, ldg, z, ldz, out, ldo, invstd, M, C, dz, lddz, dres, lddr, dgamma, dbeta, ddw_w, ddw_b, W, s)
-    if (v4) { if (L == 1) BC_BWD(4, 1); else if (L == 2) BC_BWD(4, 2); else BC_BWD(4, 3); }
-    else { if (L == 1) BC_BWD(1, 1); else if (L == 2) BC_BWD(1, 2); else BC_BWD(1, 3); }
+#define BC_BWD(V, LL, PRE) bc_backward<V, LL, PRE>(P, stages, g, ldg, z, ldz, out, ldo, invstd, M, C, dz, lddz, dres, lddr, dgamma, dbeta, ddw_w, ddw_b, W, s)
+    if (pre) { if (v4) BC_BWD(4, 1, true); else BC_BWD(1, 1, true); }
+    else if (v4) { if (L == 1) BC_BWD(4, 1, false); else if (L == 2) BC_BWD(4, 2, false); else BC_BWD(4, 3, false); }
+    else { if (L == 1) BC_BWD(1, 1, false); else if (L == 2) BC_BWD(1, 2, false); else BC_BWD(1, 3, false); }
 #undef BC_BWD
     return P2W_LAUNCH_STATUS();
+}
+
+}  // namespace
+
+extern "C" size_t p2w_bn_chain_ws_size(int32_t M, int32_t C, int32_t L) {
+    if (!bc_sizes_ok(M, C, L)) return 0;
+    return p2w_ws_bytes([&](P2wArena& a) { bc_carve(a, M, C, L); });
+}
+
+extern "C" int32_t p2w_bn_chain(const float* z, int32_t ldz, const float* res, int32_t ldr, const p2w_bn_stage* stages, int32_t L, int32_t M,
+                                int32_t C, float* out, int32_t ldo, float* mean, float* invstd, void* ws, size_t ws_bytes, p2w_stream_t stream) {
+    return bc_chain_forward(false, z, ldz, res, ldr, stages, L, M, C, out, ldo, mean, invstd, ws, ws_bytes, stream);
+}
+
+extern "C" int32_t p2w_bn_chain_bwd(const float* g, int32_t ldg, const float* z, int32_t ldz, const float* out, int32_t ldo,
+                                    const p2w_bn_stage* stages, int32_t L, const float* mean, const float* invstd, int32_t M, int32_t C, float* dz,
+                                    int32_t lddz, float* dres, int32_t lddr, float* dgamma, float* dbeta, float* ddw_w, float* ddw_b, void* ws,
+                                    size_t ws_bytes, p2w_stream_t stream) {
+    return bc_chain_backward(false, g, ldg, z, ldz, out, ldo, stages, L, mean, invstd, M, C, dz, lddz, dres, lddr, dgamma, dbeta, ddw_w, ddw_b, ws,
+                             ws_bytes, stream);
+}
+
+// ---- ReLU in front of one training-mode BatchNorm1d: the one-stage chain on relu(z)
+extern "C" size_t p2w_relu_bn_ws_size(int32_t M, int32_t C) { return p2w_bn_chain_ws_size(M, C, 1); }
+
+extern "C" int32_t p2w_relu_bn(const float* z, int32_t ldz, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                               double momentum, double eps, int32_t M, int32_t C, float* out, int32_t ldo, float* mean, float* invstd, void* ws,
+                               size_t ws_bytes, p2w_stream_t stream) {
+    const p2w_bn_stage st = {nullptr, nullptr, gamma, beta, running_mean, running_var, momentum, eps, 0};
+    return bc_chain_forward(true, z, ldz, nullptr, 0, &st, 1, M, C, out, ldo, mean, invstd, ws, ws_bytes, stream);
+}
+
+extern "C" int32_t p2w_relu_bn_bwd(const float* g, int32_t ldg, const float* z, int32_t ldz, const float* gamma, const float* mean,
+                                   const float* invstd, int32_t M, int32_t C, float* dz, int32_t lddz, float* dgamma, float* dbeta, void* ws,
+                                   size_t ws_bytes, p2w_stream_t stream) {
+    // (the chain's kernels load beta beside gamma; without a ReLU behind the BatchNorm no gradient depends on it: gamma stands in)
+    const p2w_bn_stage st = {nullptr, nullptr, gamma, gamma, nullptr, nullptr, 0.0, 0.0, 0};
+    return bc_chain_backward(true, g, ldg, z, ldz, nullptr, 0, &st, 1, mean, invstd, M, C, dz, lddz, nullptr, 0, dgamma, dbeta, nullptr, nullptr, ws,
+                             ws_bytes, stream);
 }

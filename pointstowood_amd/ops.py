@@ -25,7 +25,9 @@ trains through ``edge_layer1`` (``csrc/p2w_edge.hip``: the hoisted layer 1 of th
 segment max in one forward and one backward kernel, differentiable with respect to its input and BatchNorm's weight and bias); its
 fused eval-mode kernel and ``Net.forward`` stay inference-only.  ``InvertedResidualBlock`` (``model.py:46-85``) trains through
 ``bn_chain`` (``csrc/p2w_bnchain.hip``): everything between two of its 1x1 convolutions - depthwise convolution, training-mode
-BatchNorm1d, ReLU, up to three times, and the residual add - computed from the GEMM's output alone in both directions.
+BatchNorm1d, ReLU, up to three times, and the residual add - computed from the GEMM's output alone in both directions.  ``FPModule``
+(``model.py:142-153``) trains through ``interp_add_relu`` (``csrc/p2w_fp.hip``: layer 0 hoisted behind the interpolation, the add and the
+ReLU in the interpolation's pass) and ``relu_bn`` (``csrc/p2w_bnchain.hip``: ReLU and training-mode BatchNorm1d from the GEMM's output).
 """
 from __future__ import annotations
 
@@ -815,3 +817,198 @@ class InvertedResidualBlock(torch.nn.Module):
         out = self.project[1](_rows_conv(self.project[0], out))
         res = self.shortcut[1](_rows_conv(self.shortcut[0], x)) if len(self.shortcut) else x
         return relu(out + res)
+
+
+# --------------------------------------------------------------------------- the feature-propagation module for training
+def _interp_add_relu_forward(Pc, S, rc, rf, nbr, deg, k):
+    """H [m, C padded to a multiple of 4] of ``p2w_interp_add_relu`` (the pad columns are zeros)."""
+    (pc, C), (sc, _) = _pad4(Pc.detach()), _pad4(S.detach())
+    pc, sc = _lib.aligned16(pc), _lib.aligned16(sc)
+    m, n_c = sc.shape[0], pc.shape[0]
+    H = torch.empty((m, C), dtype=torch.float32, device=sc.device)
+    check(lib().p2w_interp_add_relu(ptr(pc), C, ptr(sc), C, ptr(rc), ptr(rf), ptr(nbr), ptr(deg), int(k), m, n_c, C, ptr(H), C, stream()),
+          "interp_add_relu")
+    return H
+
+
+class _InterpAddRelu(torch.autograd.Function):
+    """``p2w_interp_add_relu`` forward, ``p2w_interp_add_relu_bwd`` backward: gradients with respect to Pc and S.  Saved for backward:
+    the output H (its sign is the ReLU's mask) and the index tensors - neither Pc nor S."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, Pc, S, rc, rf, nbr, deg, k):
+        H = _interp_add_relu_forward(Pc, S, rc, rf, nbr, deg, k)
+        C0 = S.shape[1]
+        out = H if H.shape[1] == C0 else H[:, :C0].contiguous()
+        ctx.save_for_backward(H, rc, rf, nbr, deg)
+        ctx.k, ctx.n_c, ctx.C0, ctx.dtypes = int(k), Pc.shape[0], C0, (Pc.dtype, S.dtype)
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_out):
+        H, rc, rf, nbr, deg = ctx.saved_tensors
+        (m, C), n_c, C0, dev = H.shape, ctx.n_c, ctx.C0, H.device
+        g = _lib.aligned16(_pad4(grad_out)[0])
+        dS = torch.empty((m, C), dtype=torch.float32, device=dev)
+        dPc = torch.empty((n_c, C), dtype=torch.float32, device=dev)
+        need = int(lib().p2w_interp_add_relu_bwd_ws_size(m, ctx.k, n_c))
+        if need == 0:
+            raise RuntimeError(f"p2w_interp_add_relu_bwd_ws_size({m}, {ctx.k}, {n_c}) failed")
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        check(lib().p2w_interp_add_relu_bwd(ptr(g), C, ptr(H), C, ptr(rc), ptr(rf), ptr(nbr), ptr(deg), ctx.k, m, n_c, C, ptr(dS), C, ptr(dPc), C,
+                                            ptr(ws), ws.numel(), stream()), "interp_add_relu backward")
+        if C != C0:
+            dS, dPc = dS[:, :C0].contiguous(), dPc[:, :C0].contiguous()
+        return dPc.to(ctx.dtypes[0]), dS.to(ctx.dtypes[1]), None, None, None, None, None
+
+
+def interp_add_relu(Pc, S, pos_x, pos_y, batch_x=None, batch_y=None, k=3):
+    """``torch.relu(knn_interpolate(Pc, pos_x, pos_y, batch_x, batch_y, k) + S)`` in one HIP kernel (``csrc/p2w_fp.hip``), bit for
+    bit: layer 0 of the reference's ``FPModule`` (``model.py:142-153``) with the interpolation hoisted behind the GEMM.
+    ``knn_interpolate`` is linear in its features and its weights sum to 1, so for ``W0 = [Wc | Ws]``
+
+        ``relu(Linear0(cat[interp(xc), x_skip])) = relu(interp(xc @ Wc.T) + (x_skip @ Ws.T + b0))``:
+
+    the caller computes ``Pc = xc @ Wc.T`` [n_c, C] on the coarse rows and ``S = x_skip @ Ws.T + b0`` [m, C] on the fine rows, and
+    neither the interpolated [m, Fc] tensor nor the [m, Fc + Fs] concatenation is formed.  Any 1 <= k <= 100, any width (rows are
+    padded to a multiple of 4 floats for the kernel's 16-byte accesses).
+
+    Differentiable with respect to ``Pc`` and ``S`` (positions and batch vectors get none): ``dS = g [H > 0]`` in one pass, ``dPc`` =
+    ``knn_interpolate``'s backward of ``dS`` (``p2w_interp_bwd``'s code: no floating-point atomics, the same bits on every run).
+    Saved for backward: the output itself and the index tensors, neither ``Pc`` nor ``S``.  Computes in fp32 under autocast.
+    Without a gradient to track the forward runs alone and nothing is saved."""
+    _lib.require_cuda(Pc, S, pos_x, pos_y)
+    if not 1 <= k <= 100:
+        raise RuntimeError("interp_add_relu: k must be in 1..100")
+    if Pc.dim() != 2 or S.dim() != 2 or Pc.shape[1] != S.shape[1] or Pc.shape[0] != pos_x.shape[0] or S.shape[0] != pos_y.shape[0]:
+        raise RuntimeError("interp_add_relu: Pc [n_c, C] with pos_x [n_c, 3+], S [m, C] with pos_y [m, 3+]")
+    nbr, deg = _search("knn", pos_x, pos_y, None, batch_x, batch_y, int(k))
+    rc, rf = _xyzr(pos_x), _xyzr(pos_y)
+    if torch.is_grad_enabled() and (Pc.requires_grad or S.requires_grad):
+        return _InterpAddRelu.apply(Pc, S, rc, rf, nbr, deg, int(k))
+    H = _interp_add_relu_forward(Pc, S, rc, rf, nbr, deg, k)
+    return H if H.shape[1] == S.shape[1] else H[:, :S.shape[1]].contiguous()
+
+
+def _relu_bn_ws(M, C, dev):
+    need = int(lib().p2w_relu_bn_ws_size(M, C))
+    if need == 0:
+        raise RuntimeError(f"p2w_relu_bn_ws_size({M}, {C}) failed")
+    return torch.empty(need, dtype=torch.uint8, device=dev)
+
+
+def _relu_bn_forward(zc, gamma, beta, bn):
+    """(out, mean, invstd) of ``p2w_relu_bn`` on fp32, contiguous inputs; bn's running statistics move in place."""
+    (M, C), dev = zc.shape, zc.device
+    out = torch.empty((M, C), dtype=torch.float32, device=dev)
+    mean, invstd = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(2))
+    rm, rv = (t.detach().to(torch.float32).contiguous() for t in (bn.running_mean, bn.running_var))
+    ws = _relu_bn_ws(M, C, dev)
+    check(lib().p2w_relu_bn(ptr(zc), C, ptr(gamma), ptr(beta), ptr(rm), ptr(rv), float(bn.momentum), float(bn.eps), M, C, ptr(out), C,
+                            ptr(mean), ptr(invstd), ptr(ws), ws.numel(), stream()), "relu_bn")
+    with torch.no_grad():
+        for mine, theirs in ((rm, bn.running_mean), (rv, bn.running_var)):
+            if mine.data_ptr() != theirs.data_ptr():
+                theirs.copy_(mine)
+    return out, mean, invstd
+
+
+class _ReluBn(torch.autograd.Function):
+    """``p2w_relu_bn`` forward, ``p2w_relu_bn_bwd`` backward: gradients with respect to z, gamma and beta.  Saved for backward: z, mean,
+    invstd and gamma - no [M, C] tensor besides z itself."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, z, gamma, beta, bn):
+        zc, gc = _f32c(z), _f32c(gamma)
+        out, mean, invstd = _relu_bn_forward(zc, gc, _f32c(beta), bn)
+        ctx.save_for_backward(zc, mean, invstd, gc)
+        ctx.dtypes = (z.dtype, gamma.dtype, beta.dtype)
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_out):
+        z, mean, invstd, gamma = ctx.saved_tensors
+        (M, C), dev = z.shape, z.device
+        g = _f32c(grad_out)
+        dz = torch.empty((M, C), dtype=torch.float32, device=dev)
+        dgamma, dbeta = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(2))
+        ws = _relu_bn_ws(M, C, dev)
+        check(lib().p2w_relu_bn_bwd(ptr(g), C, ptr(z), C, ptr(gamma), ptr(mean), ptr(invstd), M, C, ptr(dz), C, ptr(dgamma), ptr(dbeta),
+                                    ptr(ws), ws.numel(), stream()), "relu_bn backward")
+        return dz.to(ctx.dtypes[0]), dgamma.to(ctx.dtypes[1]), dbeta.to(ctx.dtypes[2]), None
+
+
+def relu_bn(z, bn):
+    """``bn(torch.relu(z))`` for a ``torch.nn.BatchNorm1d`` ``bn`` in training mode on the pre-activation ``z`` [M, C] in rows: the tail
+    of every later layer of the reference's ``MLP`` (``model.py:198-202``: Linear, ReLU, BatchNorm1d).  By definition the one-stage
+    ``bn_chain`` on ``relu(z)`` - the same device code with the ReLU applied as ``z`` is loaded (``csrc/p2w_bnchain.hip``), so the output,
+    the statistics and every gradient equal ``bn_chain(torch.relu(z), [(bn, False)])`` bit for bit, without the [M, C] tensor
+    ``relu(z)`` and without its copy kept for the backward.  Forward: ``z`` read twice, the output written once; backward: ``z`` and the
+    gradient read twice, the gradient with respect to ``z`` written once (``dz = 0`` where ``z <= 0``); three launches each way.
+    Gradients go to ``z``, ``bn.weight`` and ``bn.bias`` in their dtypes.  Running statistics (unbiased variance) and
+    ``num_batches_tracked`` update as PyTorch's.  No floating-point atomics: the same bits on every run.  Computes in fp32 under
+    autocast.  Under ``no_grad`` the forward runs, the statistics move and nothing is saved.
+
+    In eval mode this is ``bn(torch.relu(z))`` itself.  ``affine=False``, ``track_running_stats=False`` and ``momentum=None`` raise
+    ``NotImplementedError``; fewer than two rows in training mode raise PyTorch's ``ValueError``."""
+    _lib.require_cuda(z)
+    if not isinstance(bn, torch.nn.BatchNorm1d):
+        raise TypeError("relu_bn: bn must be a torch.nn.BatchNorm1d")
+    if not bn.affine or not bn.track_running_stats or bn.momentum is None:
+        raise NotImplementedError("relu_bn supports BatchNorm1d(affine=True, track_running_stats=True, momentum=<float>) as the reference builds it")
+    if z.dim() != 2 or z.shape[1] != bn.num_features:
+        raise RuntimeError("relu_bn: z [M, C] with C = bn.num_features")
+    if not bn.training:
+        return bn(torch.relu(z))
+    if z.shape[0] < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {z.size()}")
+    if bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    if torch.is_grad_enabled() and (z.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad):
+        return _ReluBn.apply(z, bn.weight, bn.bias, bn)
+    return _relu_bn_forward(_f32c(z), _f32c(bn.weight), _f32c(bn.bias), bn)[0]
+
+
+class FPModule(torch.nn.Module):
+    """Drop-in for the reference's ``FPModule`` (``model.py:142-153``): the same constructor (``k``, the channel list ``NN``), ``self.NN``
+    built as the reference's ``MLP(NN)`` (``model.py:198-202``) and therefore the same ``state_dict`` keys (``NN.0.0.weight``,
+    ``NN.0.0.bias``, ``NN.1.0.*``, ``NN.1.2.*``, ...), the same
+    ``forward(x, pos, batch, x_skip, pos_skip, batch_skip) -> (x, pos_skip, batch_skip)``.
+
+    Training mode with ``x_skip`` given: layer 0 is hoisted behind the interpolation -
+    ``Pc = F.linear(x, W0[:, :Fc])`` on the coarse rows, ``S = F.linear(x_skip, W0[:, Fc:], b0)`` on the fine rows,
+    ``interp_add_relu(Pc, S, ...)`` - and every later layer is ``relu_bn(F.linear(h, Wi, bi), NN[i][2])``.  The GEMMs are PyTorch's in
+    both directions; neither the interpolated tensor nor the concatenation is formed, and no activation is kept for the backward
+    besides the GEMMs' outputs and layer 0's output.  The same function as the plain composition, other roundings.
+
+    Eval mode, ``x_skip is None`` and ``fused = False`` (class attribute, default True; set it on the class or an instance) run the
+    reference's statements one by one: ``knn_interpolate``, ``torch.cat``, ``self.NN``."""
+
+    fused = True
+
+    def __init__(self, k, NN):
+        super().__init__()
+        from torch.nn import BatchNorm1d, Linear, ReLU, Sequential
+        self.k = k
+        self.NN = Sequential(*[Sequential(*([Linear(NN[i - 1], NN[i]), ReLU()] + ([BatchNorm1d(NN[i])] if i != 1 else [])))
+                               for i in range(1, len(NN))])
+
+    def forward(self, x, pos, batch, x_skip, pos_skip, batch_skip):
+        if not (self.training and self.fused and x_skip is not None):
+            h = knn_interpolate(x, pos, pos_skip, batch, batch_skip, k=self.k)
+            if x_skip is not None:
+                h = torch.cat([h, x_skip], dim=1)
+            return self.NN(h), pos_skip, batch_skip
+        lin0, Fc = self.NN[0][0], x.shape[1]
+        if lin0.in_features != Fc + x_skip.shape[1]:
+            raise RuntimeError("FPModule: NN[0] must take x.shape[1] + x_skip.shape[1] inputs")
+        Pc = torch.nn.functional.linear(x, lin0.weight[:, :Fc])                     # layer 0 on the coarse rows, no bias
+        S = torch.nn.functional.linear(x_skip, lin0.weight[:, Fc:], lin0.bias)      # ... and on the fine rows
+        h = interp_add_relu(Pc, S, pos, pos_skip, batch, batch_skip, k=self.k)
+        for layer in list(self.NN)[1:]:
+            h = relu_bn(layer[0](h), layer[2])
+        return h, pos_skip, batch_skip

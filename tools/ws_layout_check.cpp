@@ -29,6 +29,7 @@ static std::vector<Region> g_regions;
 #include "../pointstowood_amd/csrc/p2w_edge.hip"
 #include "../pointstowood_amd/csrc/p2w_bnmax.hip"
 #include "../pointstowood_amd/csrc/p2w_bnchain.hip"
+#include "../pointstowood_amd/csrc/p2w_fp.hip"
 
 static int g_fail = 0, g_runs = 0;
 
@@ -82,6 +83,7 @@ int main() {
             for (int c : {2, 3, 8}) check("ev_carve", n, s, c, [&](P2wArena& a) { ev_carve(a, n, s, c); });
         for (int rows : {0, 1, 2, 257}) {
             check("ib_carve", n, rows, 0, [&](P2wArena& a) { ib_carve(a, n, rows); });
+            if (n <= 100003) check("fp_carve", n, rows, 0, [&](P2wArena& a) { fp_carve(a, i, 3, rows); });
             for (int C : {1, 32, 33, 67}) {
                 check("eb_carve", n, rows, C, [&](P2wArena& a) { eb_carve(a, i, rows, C); });
                 if (n > 0) check("bm_carve", n, C, 0, [&](P2wArena& a) { bm_carve(a, i, C); });
