@@ -788,6 +788,41 @@ int32_t p2w_interp_add_relu_bwd(const float* g, int32_t ldg, const float* H, int
                                 const int32_t* nbr, const int32_t* deg, int32_t kw, int32_t m, int32_t n_c, int32_t C, float* dS,
                                 int32_t ldds, float* dPc, int32_t lddp, void* ws, size_t ws_bytes, p2w_stream_t stream);
 
+/* ---- the head behind conv1 for training with one class (pointstowood_amd/ops.py: bn_relu_rowdot) ---- */
+/* model.py:242-243 on the pre-activation z[M, C] (pitch ldz) in rows: training-mode BatchNorm1d, ReLU and the 1 x C convolution,
+ *   logit[r] = fl(sum_c fl(w[c] u[r, c]) + bias),   u = relu(BN(z)),
+ * without u [M, C] or its gradient ever being stored.  gamma, beta, w are [C]; bias is a DEVICE scalar; logit is [M].  By definition
+ * the statistics and u are the one-stage p2w_bn_chain's (no depthwise convolution, ReLU behind the BatchNorm, no residual): the same
+ * device code, the fp64 column sums per P2W_BN_CHAIN_ROWS consecutive rows in ascending order, the work items in ascending order, the
+ * same rounding points of xhat, y and u = y < 0 ? 0 : y, the same running-statistics update - so mean, invstd [C] and running_* equal
+ * p2w_bn_chain (L = 1) bit for bit.  Three launches; the third replaces the chain's apply pass: z is read twice, M floats are written.
+ * The sum of a row, an order that depends on C alone: one wave takes 16 consecutive rows and sums each of them on its own; lane
+ * l = 0 .. 63 owns the columns 256 p + 4 l + e (e = 0 .. 3) of pass p = 0, 1, ...; every lane starts at +0 and adds fl(w[c] u[r, c])
+ * over its columns c < C in ascending order; the 64 lanes are then added in a butterfly (partner lane ^ 32, ^ 16, ^ 8, ^ 4, ^ 2, ^ 1),
+ * and bias is added last.  fp32, no fma, no atomics: the same bits on every run and at either access width.
+ * Access width: 16 bytes per lane when C and ldz are multiples of 4 and z, gamma, beta, w, mean, invstd are 16-byte aligned, 4 bytes
+ * otherwise (same columns per lane, same bits).  ws: 16-byte aligned (P2W_EALIGN), p2w_bn_relu_rowdot_ws_size(M, C) bytes (0 = bad
+ * sizes; too small: P2W_EWORKSPACE; one size serves both directions).  2 <= M < 2^31 - 1, C >= 1, M C <= 2^38, ldz >= C, eps >= 0,
+ * 0 <= momentum <= 1 (P2W_EINVAL); every pointer is required (P2W_ENULL).  A NaN in z poisons its column (and with it every logit), as
+ * in PyTorch.  A refused call launches nothing. */
+size_t p2w_bn_relu_rowdot_ws_size(int32_t M, int32_t C);
+int32_t p2w_bn_relu_rowdot(const float* z, int32_t ldz, const float* gamma, const float* beta, const float* w, const float* bias,
+                           float* running_mean, float* running_var, double momentum, double eps, int32_t M, int32_t C, float* logit,
+                           float* mean, float* invstd, void* ws, size_t ws_bytes, p2w_stream_t stream);
+/* Its backward, on z, the forward's mean and invstd, gamma, beta, w and the gradient g[M] of the logits.  The forward is recomputed from
+ * z with the forward's code on the forward's rounded mean and invstd, so the ReLU mask is the forward's.  With xhat = fl(fl(z - mean)
+ * invstd) and gy[r, c] = fl(g[r] w[c]) [u[r, c] > 0], formed in registers:
+ *   dbeta = sum gy,   dgamma = sum gy xhat,   dw = sum g u   per column,   dbias = sum g
+ *            fp64 terms on the fp32 values, per work item of P2W_BN_CHAIN_ROWS rows in ascending row order, the items in ascending order
+ *            (dbias: 64 chains over the items i, i + 64, ... and a butterfly over the chains), rounded to fp32 once
+ *   dz = fl(fl(fl(gy - k1) - fl(xhat k2)) fl(gamma invstd)),   k1 = dbeta / M,   k2 = dgamma / M        (pitch lddz; fp32, no fma)
+ * dz, dgamma and dbeta equal p2w_bn_chain_bwd (L = 1, ReLU) fed the materialised gradient fl(g[r] w[c]) bit for bit.  dgamma, dbeta,
+ * dw [C] and dbias (a device scalar) are written, not added to.  Three launches; z is read twice and g (M floats) twice, dz written
+ * once; no other [M, C] tensor, no atomics.  Width (dz and lddz count as well), ws, sizes and status codes as in the forward. */
+int32_t p2w_bn_relu_rowdot_bwd(const float* g, const float* z, int32_t ldz, const float* gamma, const float* beta, const float* w,
+                               const float* mean, const float* invstd, int32_t M, int32_t C, float* dz, int32_t lddz, float* dgamma,
+                               float* dbeta, float* dw, float* dbias, void* ws, size_t ws_bytes, p2w_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -139,6 +139,9 @@ SIGNATURES = {
     "p2w_interp_add_relu": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "p2w_interp_add_relu_bwd_ws_size": (_sz, [_i32, _i32, _i32]),
     "p2w_interp_add_relu_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _sz, _vp]),
+    "p2w_bn_relu_rowdot_ws_size": (_sz, [_i32, _i32]),
+    "p2w_bn_relu_rowdot": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "p2w_bn_relu_rowdot_bwd": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

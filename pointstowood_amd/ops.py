@@ -973,6 +973,98 @@ def relu_bn(z, bn):
     return _relu_bn_forward(_f32c(z), _f32c(bn.weight), _f32c(bn.bias), bn)[0]
 
 
+# --------------------------------------------------------------------------- the head behind conv1 for training
+def _head_ws(M, C, dev):
+    need = int(lib().p2w_bn_relu_rowdot_ws_size(M, C))
+    if need == 0:
+        raise RuntimeError(f"p2w_bn_relu_rowdot_ws_size({M}, {C}) failed")
+    return torch.empty(need, dtype=torch.uint8, device=dev)
+
+
+def _bn_relu_rowdot_forward(zc, gamma, beta, w, b, bn):
+    """(logit, mean, invstd) of ``p2w_bn_relu_rowdot`` on fp32, contiguous inputs; bn's running statistics move in place."""
+    (M, C), dev = zc.shape, zc.device
+    logit = torch.empty(M, dtype=torch.float32, device=dev)
+    mean, invstd = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(2))
+    rm, rv = (t.detach().to(torch.float32).contiguous() for t in (bn.running_mean, bn.running_var))
+    ws = _head_ws(M, C, dev)
+    check(lib().p2w_bn_relu_rowdot(ptr(zc), C, ptr(gamma), ptr(beta), ptr(w), ptr(b), ptr(rm), ptr(rv), float(bn.momentum), float(bn.eps),
+                                   M, C, ptr(logit), ptr(mean), ptr(invstd), ptr(ws), ws.numel(), stream()), "bn_relu_rowdot")
+    with torch.no_grad():
+        for mine, theirs in ((rm, bn.running_mean), (rv, bn.running_var)):
+            if mine.data_ptr() != theirs.data_ptr():
+                theirs.copy_(mine)
+    return logit, mean, invstd
+
+
+class _BnReluRowdot(torch.autograd.Function):
+    """``p2w_bn_relu_rowdot`` forward, ``p2w_bn_relu_rowdot_bwd`` backward: gradients with respect to z, gamma, beta, the weight and the
+    bias.  Saved for backward: z and [C] vectors - neither ``relu(bn(z))`` nor its gradient exists."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, z, gamma, beta, weight, bias, bn):
+        zc, gc, bc, wc = _f32c(z), _f32c(gamma), _f32c(beta), _lib.aligned16(_f32c(weight.reshape(-1)))
+        logit, mean, invstd = _bn_relu_rowdot_forward(zc, gc, bc, wc, _f32c(bias.reshape(-1)), bn)
+        ctx.save_for_backward(zc, mean, invstd, gc, bc, wc)
+        ctx.like = [(t.dtype, t.shape) for t in (z, gamma, beta, weight, bias)]
+        return logit
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_out):
+        z, mean, invstd, gamma, beta, w = ctx.saved_tensors
+        (M, C), dev = z.shape, z.device
+        g = _f32c(grad_out)
+        dz = torch.empty((M, C), dtype=torch.float32, device=dev)
+        dgamma, dbeta, dw = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(3))
+        dbias = torch.empty(1, dtype=torch.float32, device=dev)
+        ws = _head_ws(M, C, dev)
+        check(lib().p2w_bn_relu_rowdot_bwd(ptr(g), ptr(z), C, ptr(gamma), ptr(beta), ptr(w), ptr(mean), ptr(invstd), M, C, ptr(dz), C,
+                                           ptr(dgamma), ptr(dbeta), ptr(dw), ptr(dbias), ptr(ws), ws.numel(), stream()),
+              "bn_relu_rowdot backward")
+        return (*[gr.to(dt).reshape(shape) for gr, (dt, shape) in zip((dz, dgamma, dbeta, dw, dbias), ctx.like)], None)
+
+
+def bn_relu_rowdot(z, bn, weight, bias):
+    """``F.linear(torch.relu(bn(z)), weight, bias)[:, 0]`` for a ``torch.nn.BatchNorm1d`` ``bn`` in training mode and ONE output channel,
+    on the pre-activation ``z`` [M, C] in rows: the reference's head behind ``conv1`` (``model.py:242-243``) as the trainer builds it,
+    ``num_classes = 1``.  ``weight`` is [1, C] or [1, C, 1] (``conv2.weight``), ``bias`` has one element; the result is [M] float32.
+
+    One operator (``csrc/p2w_head.hip``): the statistics are the one-stage ``bn_chain``'s own device code (the same bits), and the
+    third launch reads ``z`` once more and writes M floats - ``relu(bn(z))`` [M, C] is never formed, nor is its gradient on the way
+    back: the backward takes three column sums per work item from ``z`` and the M gradients of the logits, reduces them in a fixed
+    order and writes ``dz`` in one more pass over ``z``.  ``z`` is read twice in each direction.  Saved for backward: ``z`` and [C]
+    vectors.  Gradients go to ``z``, ``bn.weight``, ``bn.bias``, ``weight`` and ``bias`` in their dtypes and shapes.  A row's sum runs
+    in an order fixed by C alone (``include/p2w.h``); no floating-point atomics: the same bits on every run.  Running statistics
+    (unbiased variance) and ``num_batches_tracked`` update as PyTorch's.  Computes in fp32 under autocast.  Under ``no_grad`` the
+    forward runs, the statistics move and nothing is saved.
+
+    In eval mode this is the plain composition on the running statistics.  ``affine=False``, ``track_running_stats=False`` and
+    ``momentum=None`` raise ``NotImplementedError``; fewer than two rows in training mode raise PyTorch's ``ValueError``."""
+    _lib.require_cuda(z, weight, bias)
+    if not isinstance(bn, torch.nn.BatchNorm1d):
+        raise TypeError("bn_relu_rowdot: bn must be a torch.nn.BatchNorm1d")
+    if not bn.affine or not bn.track_running_stats or bn.momentum is None:
+        raise NotImplementedError("bn_relu_rowdot supports BatchNorm1d(affine=True, track_running_stats=True, momentum=<float>) as the "
+                                  "reference builds it")
+    if z.dim() != 2 or z.shape[1] != bn.num_features:
+        raise RuntimeError("bn_relu_rowdot: z [M, C] with C = bn.num_features")
+    C = z.shape[1]
+    if weight.dim() not in (2, 3) or tuple(weight.shape) != (1, C, 1)[:weight.dim()] or bias is None or bias.numel() != 1:
+        raise RuntimeError("bn_relu_rowdot: weight [1, C] or [1, C, 1] and a bias of one element (one output channel)")
+    if not bn.training:
+        return torch.nn.functional.linear(torch.relu(bn(z)), weight.reshape(1, C), bias.reshape(1))[:, 0]
+    if z.shape[0] < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {z.size()}")
+    if bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (z, bn.weight, bn.bias, weight, bias)):
+        return _BnReluRowdot.apply(z, bn.weight, bn.bias, weight, bias, bn)
+    return _bn_relu_rowdot_forward(_f32c(z), _f32c(bn.weight), _f32c(bn.bias), _lib.aligned16(_f32c(weight.reshape(-1))),
+                                   _f32c(bias.reshape(-1)), bn)[0]
+
+
 class FPModule(torch.nn.Module):
     """Drop-in for the reference's ``FPModule`` (``model.py:142-153``): the same constructor (``k``, the channel list ``NN``), ``self.NN``
     built as the reference's ``MLP(NN)`` (``model.py:198-202``) and therefore the same ``state_dict`` keys (``NN.0.0.weight``,

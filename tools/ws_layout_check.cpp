@@ -30,6 +30,7 @@ static std::vector<Region> g_regions;
 #include "../pointstowood_amd/csrc/p2w_bnmax.hip"
 #include "../pointstowood_amd/csrc/p2w_bnchain.hip"
 #include "../pointstowood_amd/csrc/p2w_fp.hip"
+#include "../pointstowood_amd/csrc/p2w_head.hip"
 
 static int g_fail = 0, g_runs = 0;
 
@@ -89,6 +90,7 @@ int main() {
                 if (n > 0) check("bm_carve", n, C, 0, [&](P2wArena& a) { bm_carve(a, i, C); });
                 if (n > 1 && rows == 1)
                     for (int L = 1; L <= P2W_BN_CHAIN_MAX; ++L) check("bc_carve", n, C, L, [&](P2wArena& a) { bc_carve(a, i, C, L); });
+                if (n > 1 && rows == 1) check("hd_carve", n, C, 0, [&](P2wArena& a) { hd_carve(a, i, C); });
             }
         }
     }
