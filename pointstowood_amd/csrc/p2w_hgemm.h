@@ -499,10 +499,17 @@ __device__ __forceinline__ void gemm_epilogue_dispatch16(const f32x4 (&acc)[RT16
 // ds_read_b128 of one chunk index by 16 different rows spreads over all 16 slots of the 256-byte bank row: conflict-free.
 // A DMA piece (one wave-instruction, 1 KiB) = 8 image rows: lane L -> row 8g + (L >> 3), stored chunk L & 7, reading the
 // source chunk (L & 7) ^ swizzle: 8 rows x 128 contiguous bytes = 8 whole cache lines per piece.
-// DMA issue.  8-wave tiles (HALF): waves 0..3 issue the whole stage behind the barrier while waves 4..7 - their SIMD
+// DMA issue.  A piece's source is a scalar base + a 32-bit lane offset (the saddr form of global_load_lds: see "DMA sources"
+// in gemm_hp_body), so a piece costs scalar instructions only and the sources hold two vector registers, not 2 NI.
+// 8-wave tiles (HALF): waves 0..3 issue the whole stage behind the barrier while waves 4..7 - their SIMD
 // partners, which the hardware's oldest-first arbitration makes the losers of every slab (in-kernel stamps: wave 0 waits
 // 39 % of the loop at the barrier, wave 4 4 %) - start on the MFMAs at once: the issue time of one half is the other half's
-// uncontested MFMA time.  4-wave tiles: every wave spreads its pieces over the first half of the slab's MFMAs instead of
+// uncontested MFMA time.  What bounds a slab is therefore waves 4..7, which run the slab's tail alone on their SIMDs: their A
+// fragment reads are issued a row tile ahead (below) so that no LDS latency stands in the open there.  That is worth 1 - 2 %
+// on the long-K 256 x 256 launches and nothing a step-level A/B can tell from noise; launches of one to four slabs per tile
+// measured up to 5 % slower than with per-lane pointers on one box and the same on another (docs/LAB_NOTES.md).  A static
+// s_setprio 1 for waves 4..7 on top measured nothing.
+// 4-wave tiles: every wave spreads its pieces over the first half of the slab's MFMAs instead of
 // issuing them as one burst behind the barrier: a piece costs ~60-180 issue cycles, and with every wave of the workgroup
 // re-aligned by the barrier a burst leaves all four MFMA pipes idle for ~1000 cycles of a ~3000-cycle slab.
 //
@@ -561,15 +568,39 @@ __device__ __forceinline__ void gemm_hp_body(const _Float16* __restrict__ A, int
         return;
     }
 
-    const _Float16* src[NI];
-    auto setup_src = [&](int mt_, int nt_) {   // per-lane DMA sources of a tile (LDS image and DMA pieces: see above)
+    // DMA sources: a wave-uniform 64-bit byte address per operand (the tile's first row at the K offset of the next slab to
+    // issue, in scalar registers) + ONE 32-bit byte offset per lane and operand, computed once per kernel: the piece's row
+    // within the tile (the W rows permuted: w_stage_row16) x the pitch + the lane's source chunk.  Piece i of an issuing wave is
+    // rows + 8 NWI i of piece 0, for A and for the permuted W rows alike (w_stage_row16(rho + 32) = w_stage_row16(rho) + 32),
+    // and the chunk swizzle does not depend on i (8 NWI is a multiple of 16): piece i adds i x 8 NWI x pitch to the scalar
+    // base, the K advance of a slab is a scalar add - no vector instruction and no vector register per piece.  (16 per-lane
+    // 64-bit pointers held 32 VGPRs and cost two v_lshl_add_u64 per piece.)  The cut last row tile ((mt + 1) BM > M,
+    // wave-uniform) clamps its rows to M - 1: see dma_clamped (8-wave tiles) and issue_piece (4-wave tiles).
+    constexpr int IA = BM / (8 * NWI);                    // pieces 0 .. IA-1 of an issuing wave are A rows, the rest W rows
+    static_assert(BM % (8 * NWI) == 0 && (8 * NWI) % 32 == 0, "pieces of a wave must be whole 32-row steps apart");
+    const unsigned a_pitch_b = 2u * (unsigned)a_pitch, w_pitch_b = 2u * (unsigned)w_pitch;   // bytes (the launcher bounds BM x pitch)
+    const unsigned a_step = 8u * NWI * a_pitch_b, w_step = 8u * NWI * w_pitch_b;   // (a part of BM x pitch: 32-bit)
+    const bool issuer = wave < NWI;                       // wave-uniform
+    const int prow = 8 * (wave % NWI) + (lane >> 3);      // row of piece 0 within the operand's rows of the stage
+    const unsigned pch = 16u * (unsigned)((lane & 7) ^ ((prow >> 1) & 7));
+    const unsigned offA_l = (unsigned)prow * a_pitch_b + pch, offW_l = (unsigned)w_stage_row16(prow) * w_pitch_b + pch;
+    unsigned long long a_cur = 0, w_cur = 0;              // wave-uniform byte addresses: tile base + K offset of the next slab to issue
+    bool a_edge = false;                                  // the tile's last rows lie beyond M: clamp (their results are never stored)
+    int a_rmax = 0;                                       // ... to this row of the tile
+    unsigned offA_p[HALF ? 1 : IA] = {};                  // 4-wave tiles: the lane's offset of every A piece (issue_piece)
+    auto uniform64 = [](unsigned long long v) {
+        return (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v) |
+               ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32)) << 32);
+    };
+    auto setup_src = [&](int mt_, int nt_, int k0) {   // DMA sources of a tile from K offset k0 on (LDS image and DMA pieces: see above)
+        if (HALF && !issuer) return;                   // (waves 4..7 of an 8-wave tile issue nothing)
+        a_cur = uniform64((unsigned long long)(uintptr_t)(A + (size_t)mt_ * BM * a_pitch + k0));
+        w_cur = uniform64((unsigned long long)(uintptr_t)(Wh + (size_t)nt_ * BN * w_pitch + k0));
+        a_edge = (mt_ + 1) * BM > M;
+        a_rmax = M - 1 - mt_ * BM;
+        if constexpr (!HALF) {
 #pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const int g = (wave % NWI) + NWI * i;
-            const int row = 8 * g + (lane >> 3);
-            const int c = (lane & 7) ^ ((row >> 1) & 7);
-            if (g < BM / 8) src[i] = A + (size_t)min(mt_ * BM + row, M - 1) * a_pitch + 8 * c;
-            else src[i] = Wh + (size_t)(nt_ * BN + w_stage_row16(row - BM)) * w_pitch + 8 * c;
+            for (int i = 0; i < IA; ++i) offA_p[i] = (unsigned)min(prow + 8 * NWI * i, a_rmax) * a_pitch_b + pch;
         }
     };
     // The DMA is issued through inline asm: hipcc never emits a COUNTED vmcnt while a global_load_lds it knows about is
@@ -578,13 +609,51 @@ __device__ __forceinline__ void gemm_hp_body(const _Float16* __restrict__ A, int
     // Hidden from its bookkeeping, the compiler's own waits can only become stricter than needed, never weaker (the
     // counter retires in order); the slab protocol below waits for the DMA by hand.
     const unsigned lds_base = (unsigned)(uintptr_t)(lds_vp)S;
-    auto issue_piece = [&](int i, int stage, int k0) {
-        const int g = (wave % NWI) + NWI * i;
-        const unsigned dst = lds_base + (unsigned)(stage * STAGE_CH + g * 64) * 16u;
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
-                     :: "v"(src[i] + k0), "s"(dst) : "m0", "memory");
+    // s_nop 3: a scalar register written by a VECTOR instruction needs 5 wait states before a memory instruction reads it as
+    // its base, and the compiler pads nothing for the instructions inside an asm statement.  The bases are computed by scalar
+    // instructions, but the kernel spills scalar registers to VGPR lanes and may reload a base (v_readlane, or the
+    // v_readfirstlane of setup_src) directly in front of a piece: s_mov + s_nop 3 are the 5 states, whatever stands before.
+    // (It also covers the one state between the write of m0 and the load.)  In dma_clamped the four vector instructions do it.
+    auto dma = [&](unsigned off, unsigned long long base, unsigned dst) {
+        asm volatile("s_mov_b32 m0, %2\n\ts_nop 3\n\tglobal_load_lds_dwordx4 %0, %1"
+                     :: "v"(off), "s"(base), "s"(dst) : "m0", "memory");
     };
-    const bool issuer = wave < NWI;   // wave-uniform
+    // ... of a cut row tile: the lane's offset from the tile's base, its row clamped, computed inside the statement (as plain
+    // C++ the compiler computes it ahead of the branch for every tile and keeps it in registers)
+    auto dma_clamped = [&](int row_step, unsigned dst) {
+        unsigned off;
+        asm volatile("v_add_u32 %0, %1, %2\n\tv_min_i32 %0, %3, %0\n\tv_mul_lo_u32 %0, %0, %4\n\tv_add_u32 %0, %0, %5\n\t"
+                     "s_mov_b32 m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %6"
+                     : "=&v"(off) : "s"(row_step), "v"(prow), "s"(a_rmax), "s"(a_pitch_b), "v"(pch), "s"(a_cur), "s"(dst) : "m0", "memory");
+    };
+    // The pieces of a stage are issued in ascending order, each from a running scalar address: + one step per piece, two
+    // scalar adds (a table of i x step per piece costs more scalar registers than the kernel has left)
+    unsigned long long a_run = 0, w_run = 0;
+    auto stage_dst = [&](int stage) {   // LDS byte address of the wave's piece 0 in a stage; piece i: + i NWI KiB
+        return (unsigned)__builtin_amdgcn_readfirstlane(lds_base + (unsigned)(stage * STAGE_CH + (wave % NWI) * 64) * 16u);
+    };
+    // 4-wave tiles issue their pieces one by one between the MFMA groups: a branch per piece there would cut the MFMA stream,
+    // so they keep one offset per A piece, clamped for every tile alike when the tile is set up (IA <= 4 registers)
+    auto issue_piece = [&](int i, unsigned dst0) {
+        const unsigned dst = dst0 + (unsigned)(i * NWI * 1024);
+        if (i == IA) w_run = w_cur;
+        if (i >= IA) { dma(offW_l, w_run, dst); w_run += w_step; }
+        else dma(offA_p[HALF ? 0 : i], a_cur, dst);
+    };
+    auto issue_stage = [&](int stage) {   // a whole stage as one burst: one branch for the cut row tile, not one per piece
+        const unsigned dst0 = stage_dst(stage);
+        a_run = a_cur; w_run = w_cur;
+        if (a_edge) {
+#pragma unroll
+            for (int i = 0; i < IA; ++i) dma_clamped(8 * NWI * i, dst0 + (unsigned)(i * NWI * 1024));
+        } else {
+#pragma unroll
+            for (int i = 0; i < IA; ++i) { dma(offA_l, a_run, dst0 + (unsigned)(i * NWI * 1024)); a_run += a_step; }
+        }
+#pragma unroll
+        for (int i = IA; i < NI; ++i) { dma(offW_l, w_run, dst0 + (unsigned)(i * NWI * 1024)); w_run += w_step; }
+    };
+    auto advance_src = [&]() { a_cur += 2 * 64; w_cur += 2 * 64; };   // one slab = 64 halfs of every row, in every precision
     // fragment read offsets (bytes within a stage) of plane 0: lane (row l & 15 of a 16-row tile, k octet l >> 4) reads the
     // chunk of its octet; plane 1 (f16x3: lo; single plane: k 32..63) = ^ 64
     constexpr int RT16 = 2 * RT, CT16 = 2 * CT;
@@ -600,15 +669,19 @@ __device__ __forceinline__ void gemm_hp_body(const _Float16* __restrict__ A, int
         const int rb = BM + wc * 32 * CT + 16 * t + r16;
         offB[t] = (rb * 8 + (kg ^ ((rb >> 1) & 7))) * 16;
     }
-    setup_src(mt, nt);
-    if (issuer) {
+    setup_src(mt, nt, SK ? sk_s0 * 64 : 0);
+    if constexpr (HALF) {
+        if (issuer) issue_stage(0);
+    } else {
+        const unsigned dst0 = stage_dst(0);
 #pragma unroll
-        for (int i = 0; i < NI; ++i) issue_piece(i, 0, SK ? sk_s0 * 64 : 0);
+        for (int i = 0; i < NI; ++i) issue_piece(i, dst0);
     }
+    advance_src();
     int gs = 0;        // slabs done by this workgroup: stage of the current slab = gs & 1
     bool landed = false;   // the DMA of the slab about to start has been waited for already (behind the previous tile's epilogue)
     f32x4 acc[RT16][CT16];
-    h8 ah[RT16 / 2], al[RT16 / 2], bh[CT16], bl[CT16];   // A fragments of one half of the wave's row tiles, B of all column tiles
+    h8 ah[2], al[2], bh[CT16], bl[CT16];   // A fragments of two row tiles (the one in use, the one being read), B of all column tiles
     // one slab.  LAST: the slab behind it belongs to the next tile (mtn, ntn) - or, past the last tile, is a replay nobody reads
     auto slab = [&](int s, auto last_c, int mtn, int ntn) {
         constexpr bool LAST = decltype(last_c)::value;
@@ -620,52 +693,62 @@ __device__ __forceinline__ void gemm_hp_body(const _Float16* __restrict__ A, int
         landed = false;
         __builtin_amdgcn_s_barrier();   // slab gs has landed for every wave, the other stage is free
         asm volatile("" ::: "memory");
-        if constexpr (LAST) setup_src(mtn, ntn);
+        if constexpr (LAST) setup_src(mtn, ntn, 0);
         constexpr int HR = RT16 / 2;                 // row tiles per half
         constexpr int NG = 2 * HR * CT16;            // tile pairs (MFMA groups) of a slab
         constexpr int GAP = (NG / (2 * NI)) > 0 ? NG / (2 * NI) : 1;
-        const int k_next = LAST ? 0 : (s + 1) * 64;
         if constexpr (HALF) {
-            if (issuer) {
-#pragma unroll
-                for (int i = 0; i < NI; ++i) issue_piece(i, (gs + 1) & 1, k_next);
-            }
+            if (issuer) issue_stage((gs + 1) & 1);
         }
         const char* st = S + (size_t)(gs & 1) * STAGE_CH * 16;
-#pragma unroll
-        for (int t = 0; t < CT16; ++t) {
+        const unsigned dst_next = HALF ? 0u : stage_dst((gs + 1) & 1);
+        // Fragment reads run one row tile ahead: the A fragments of row tile t + 1 are read into the other (ah, al) set behind
+        // the first of the CT16 MFMA groups of row tile t, so their LDS latency lies behind the remaining groups (9 MFMAs in
+        // f16x3) instead of behind one MFMA.  The scheduling fences pin that order: left alone, the compiler sinks every read to
+        // just in front of its first use.  Top of the slab: what the first MFMAs need (A tile 0, B tile 0) is read first.
+        auto read_a = [&](int t) {
+            al[t & 1] = *reinterpret_cast<const h8*>(st + (offA[t] ^ 64));
+            ah[t & 1] = *reinterpret_cast<const h8*>(st + offA[t]);
+        };
+        auto read_b = [&](int t) {
             bh[t] = *reinterpret_cast<const h8*>(st + offB[t]);
             bl[t] = *reinterpret_cast<const h8*>(st + (offB[t] ^ 64));
-        }
+        };
+        read_a(0);
+        read_b(0);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
+        for (int t = 1; t < CT16; ++t) read_b(t);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int t = 0; t < HR; ++t) {
-                ah[t] = *reinterpret_cast<const h8*>(st + offA[hh * HR + t]);
-                al[t] = *reinterpret_cast<const h8*>(st + (offA[hh * HR + t] ^ 64));
-            }
+        for (int t = 0; t < RT16; ++t) {
 #pragma unroll
-            for (int i = 0; i < HR; ++i)
-#pragma unroll
-                for (int j = 0; j < CT16; ++j) {
-                    f32x4& c = acc[hh * HR + i][j];
-                    if constexpr (PREC == 0) {
-                        c = h_mfma16<PREC>(al[i], bh[j], c);
-                        c = h_mfma16<PREC>(ah[i], bl[j], c);
-                        c = h_mfma16<PREC>(ah[i], bh[j], c);
-                    } else {
-                        c = h_mfma16<PREC>(ah[i], bh[j], c);
-                        c = h_mfma16<PREC>(al[i], bl[j], c);
-                    }
-                    if constexpr (!HALF) {   // 4-wave tile: every wave spreads its pieces over the first half of its MFMAs
-                        const int g = (hh * HR + i) * CT16 + j;
-                        if ((g % GAP) == GAP - 1 && g / GAP < NI) {
-                            issue_piece(g / GAP, (gs + 1) & 1, k_next);
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
+            for (int j = 0; j < CT16; ++j) {
+                f32x4& c = acc[t][j];
+                if constexpr (PREC == 0) {
+                    c = h_mfma16<PREC>(al[t & 1], bh[j], c);
+                    c = h_mfma16<PREC>(ah[t & 1], bl[j], c);
+                    c = h_mfma16<PREC>(ah[t & 1], bh[j], c);
+                } else {
+                    c = h_mfma16<PREC>(ah[t & 1], bh[j], c);
+                    c = h_mfma16<PREC>(al[t & 1], bl[j], c);
+                }
+                if (j == 0) {   // (behind the first group: the MFMAs that last read the other set are then past their operand reads)
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (t + 1 < RT16) read_a(t + 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if constexpr (!HALF) {   // 4-wave tile: every wave spreads its pieces over the first half of its MFMAs
+                    const int g = t * CT16 + j;
+                    if ((g % GAP) == GAP - 1 && g / GAP < NI) {
+                        issue_piece(g / GAP, dst_next);
+                        __builtin_amdgcn_sched_barrier(0);
                     }
                 }
+            }
+            __builtin_amdgcn_sched_barrier(0);
         }
+        advance_src();
         ++gs;
     };
     if constexpr (SK) {
@@ -765,6 +848,9 @@ static int32_t launch_gemm_h(const _Float16* Ah, int32_t ldh_a, const _Float16* 
     if (ep.imeta) flags = (flags & ~P2W_GEMM_TILE_256) | P2W_GEMM_TILE_128;   // the interpolated residual lives in the 128 x 128 kernel only
     if ((ldh_a % KA) != 0 || ldh_a < Kpad) return P2W_EINVAL;     // K padding must exist (and be zero) in A as well
     if (out_h2 && (ldh_o & 7)) return P2W_EINVAL;
+    // the DMA addresses a tile's rows as a 64-bit tile base + a 32-bit byte offset per lane (gemm_hp_body): the rows of the
+    // largest tile must lie within 2 GiB of its first (W's pitch, Kpad, is at most A's)
+    if ((size_t)256 * HCfg<PREC>::planes * (size_t)ldh_a * 2 >= ((size_t)1 << 31)) return P2W_EINVAL;
     const int hcols = ldh_o < (N + KA - 1) / KA * KA ? ldh_o : (N + KA - 1) / KA * KA;   // outputs + zero pad to the K-slab boundary
     OutArgs o = {out_f32, ldo, out_h2, ldh_o, hcols, dotw, part, ldpart};
     // 256x256 tiles halve the L2->LDS bytes per MFMA; they need enough tiles to fill the CUs and a wide N:
