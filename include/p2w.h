@@ -355,6 +355,51 @@ int32_t p2w_poly1_focal(const float* logits, const float* labels, const float* w
                         double gamma, double alpha, double label_smoothing, double eps, float* loss, float* dloss, double* sum,
                         void* ws, size_t ws_bytes, p2w_stream_t stream);
 
+/* The training feed: the voxels ids[0..B) of a device-resident training set gathered, augmented, centred and collated into one batch -
+ * TrainingDataset.__getitem__ (pointstowood/src/trainer.py:46-60), augmentations (pointstowood/src/augmentation.py:41-55: silence or
+ * perturb the reflectance, rotate_3d) and PyG's collation, with the decisions and the rotation matrices made by the host (plan).
+ * In : xyzr[n_set] float4 rows (x, y, z, reflectance) and y[n_set] float32 = the whole set, set_ptr[V + 1] int64 (ascending, set_ptr[0]
+ *      = 0, set_ptr[V] = n_set); ids[B] int32 = the batch's voxels, DISTINCT; out_ptr[B + 1] int64 (out_ptr[0] = 0, out_ptr[b + 1] -
+ *      out_ptr[b] = the length of voxel ids[b], out_ptr[B] = n); plan[V] records indexed by VOXEL ID; seed, epoch; noise[n] (optional:
+ *      NULL) = the standard-deviation-0.1 noise of the perturbed rows, by OUTPUT row, in place of the generator.  All DEVICE memory.
+ * Out: pos[n][3], reflectance[n], y[n] float32, batch[n] int64 (= b), sf[B] float32, nonfinite[B] int32; words_out[n][4] uint32
+ *      (optional: NULL) = the generator's four words of every row (whatever its voxel's refl_mode).
+ * Arithmetic of voxel v = ids[b], rows i = 0 .. len - 1, every rounding point:
+ *   mean  = S / len in float64, S = the float64 sum of the float32 coordinates (conversions exact): one partial per P2W_FEED_CHUNK
+ *           consecutive rows of the voxel (lanes by a fixed xor tree, waves in order), the partials added in ascending order;
+ *   d     = fl32(x - mean): the subtraction in float64, rounded ONCE to float32 (centre first, rotate after: mean(x R) = mean(x) R, and
+ *           plot coordinates of hundreds of metres then never meet a float32 product);
+ *   p     = d when !rotate, else p_j = fmaf(d_z, R[6 + j], fmaf(d_y, R[3 + j], fl32(d_x * R[j]))): three roundings per coordinate;
+ *           R (row-major, p = d R) = roll pitch yaw of rotate_3d, formed by the host in float64 from the float32 cos / sin and rounded;
+ *   refl  = r (refl_mode 0), +0.0 (1), fl32(r + e) (2) with e = noise[row] or fl32(0.1f * z);
+ *   z     : Philox4x32-10, counter = (i, v, epoch, P2W_FEED_STREAM), key = (seed & 0xffffffff, seed >> 32), words w0 .. w3;
+ *           u1 = fl32((w0 >> 8) + 1) * 2^-24 in (0, 1], u2 = fl32(w1 >> 8) * 2^-24 in [0, 1), both exact;
+ *           z = fl32(sqrtf(fl32(-2 * logf(u1))) * cosf(fl32(6.2831855f * u2))) (Box-Muller's cosine branch; w2, w3 unused) - so a
+ *           voxel's noise depends on (seed, epoch, v, i) alone, never on the batch or the slot;
+ *   sf[b] = max_i sqrtf(fl32(fl32(fl32(p_x p_x) + fl32(p_y p_y)) + fl32(p_z p_z))) of the WRITTEN p, no contraction: an integer
+ *           atomic maximum of the sign-cleared bit patterns (order-independent: the same bits on every run; a NaN's pattern is above
+ *           infinity's, so a NaN row gives a NaN sf, as torch.max does); 0 for an empty voxel;
+ *   nonfinite[b] = rows with a non-finite x, y, z or INPUT reflectance.  They are passed through (a non-finite coordinate makes the
+ *           voxel's mean, and with it all its positions and its sf, non-finite, as in the reference).
+ * Two launches, no memset (the first launch zeroes sf and nonfinite), no host synchronisation and no host read.  0 <= n, n_set <= 2^40,
+ * B >= 0, V >= 1 (P2W_EINVAL); B = 0 or n = 0: P2W_OK, nothing written, nothing launched.  xyzr, plan and ws 16-byte aligned
+ * (P2W_EALIGN); every pointer but noise and words_out required (P2W_ENULL); ws: p2w_train_feed_ws_size(n, B) bytes (n / P2W_FEED_CHUNK +
+ * B chunks; 0 = bad sizes; too small: P2W_EWORKSPACE).  A refused call launches nothing.  Offsets are clamped to their arrays and an id
+ * outside [0, V) is an empty voxel, so no access leaves the arrays whatever the index arrays hold; len < 2^32. */
+#define P2W_FEED_CHUNK 256
+#define P2W_FEED_STREAM 0x50325746u /* "P2WF": the counter word that keeps this stream apart from later users of the generator */
+typedef struct p2w_feed_plan {
+    int32_t refl_mode; /* 0 keep, 1 zero, 2 perturb */
+    int32_t rotate;    /* 0: R is the identity and is not applied */
+    float R[9];
+    int32_t reserved;  /* 48-byte records */
+} p2w_feed_plan;
+size_t p2w_train_feed_ws_size(int64_t n, int32_t B);
+int32_t p2w_train_feed(const float* xyzr, const float* y, const int64_t* set_ptr, int64_t n_set, int32_t V, const int32_t* ids,
+                       const int64_t* out_ptr, int32_t B, int64_t n, const p2w_feed_plan* plan, uint64_t seed, uint32_t epoch,
+                       const float* noise, float* pos_out, float* refl_out, float* y_out, int64_t* batch_out, float* sf_out,
+                       int32_t* nonfinite_out, uint32_t* words_out, void* ws, size_t ws_size, p2w_stream_t stream);
+
 /* PointCloudClassifier.compute_labels (predicter.py:112-127) over a neighbour table nbr[n,k] (indices into pred /
  * prob, deg[i] valid entries): pwood_out = median of the neighbours' probabilities (np.median: mean of the two middle
  * values for an even count); label_out: any_wood != 1 -> 1 if any neighbour's prediction > any_wood else 0;

@@ -41,6 +41,7 @@ LOSS_CHUNK = 4096                                                               
 EDGE_CHUNK = 1024                                                                                  # P2W_EDGE_CHUNK
 BN_GROUP = 16                                                                                      # P2W_BN_GROUP
 BN_CHAIN_MAX, BN_CHAIN_ROWS = 3, 32                                                                # P2W_BN_CHAIN_*
+FEED_CHUNK, FEED_STREAM = 256, 0x50325746                                                          # P2W_FEED_*
 
 SIGNATURES = {
     "p2w_version": (_i32, []),
@@ -90,6 +91,9 @@ SIGNATURES = {
     "p2w_poly1_focal_ws_bytes": (_sz, [C.c_int64]),
     "p2w_poly1_focal": (_i32, [_vp, _vp, _vp, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp,
                                _vp, _sz, _vp]),
+    "p2w_train_feed_ws_size": (_sz, [C.c_int64, _i32]),
+    "p2w_train_feed": (_i32, [_vp, _vp, _vp, C.c_int64, _i32, _vp, _vp, _i32, C.c_int64, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp,
+                              _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "p2w_tile_bbox": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "p2w_tile_bbox_count": (_i32, [_i32, _i32]),
     "p2w_stem": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp]),

@@ -1,0 +1,226 @@
+"""The reference's training loop (``pointstowood/src/trainer.py:96-320`` ``SemanticTraining``) over this package's parts:
+``train.Net``, two ``feed.TrainingFeed`` s over device-resident ``feed.TrainingSet`` s, ``loss.Poly1FocalLoss`` and ``loss.EpochScores``.
+
+Kept from the reference: ``Net(num_classes=1)``; ``shuffle=True, drop_last=True`` loaders, the held-out one in ``mode="test"`` with
+``batch_size // 2`` voxels; ``Poly1FocalLoss(reduction="mean", gamma=2.0, alpha=None, label_smoothing=0.1)``; autocast,
+``GradScaler(init_scale=512)``, ``clip_grad_norm_(1.0)``; AdamW with ``OneCycleLR`` (``--tune``: the cosine schedule with warm restarts)
+stepped once per epoch; the history rows and their column order (7 columns, 11 with ``--test``) written with ``np.savetxt`` after every
+epoch; ``{'model_state_dict': ...}`` checkpoints at ``args.checkpoints``; the ``ba-`` / ``f1-`` / ``precision-`` best-model files under
+its epoch conditions; the final model.
+
+Deviations (route A-train): no per-step ``deepcopy(state_dict)`` with a try / except rollback (``GradScaler`` already
+skips a step with non-finite gradients); no ``set_detect_anomaly``; no ``.item()`` per batch - ``EpochScores`` reads the device once
+per epoch; and the early-stop counter PERSISTS across epochs: the reference resets it to 0 at every epoch, so its ``>= 10`` can never
+fire - what is built is the intent its message documents (training accuracy decreased for 10 consecutive epochs).
+"""
+from __future__ import annotations
+
+import math
+import os
+from collections import OrderedDict
+
+import numpy as np
+import torch
+
+from . import train as _train
+from .feed import TrainingFeed, TrainingSet
+from .loss import EpochScores, Poly1FocalLoss
+
+
+class CosineAnnealingWarmupRestarts:
+    """Cosine annealing with a linear warm-up and warm restarts, from the schedule's definition (the reference takes a third-party
+    class of this name; only its ``step()``-without-argument path is used there and provided here).
+
+    A cycle has ``cycle_steps`` steps (``first_cycle_steps`` at first; after a cycle ``int((cycle_steps - warmup_steps) * cycle_mult) +
+    warmup_steps``).  At step t of a cycle the rate is ``min_lr + (max_lr - min_lr) * t / warmup_steps`` for ``t < warmup_steps`` and
+    ``min_lr + (max_lr - min_lr) * (1 + cos(pi * (t - warmup_steps) / (cycle_steps - warmup_steps))) / 2`` after; cycle c's ``max_lr`` is
+    ``max_lr * gamma ** c``.  Construction sets every group's rate to ``min_lr`` and then takes step 0 (the rate stays ``min_lr``)."""
+
+    def __init__(self, optimizer, first_cycle_steps: int, cycle_mult: float = 1.0, max_lr: float = 0.1, min_lr: float = 0.001,
+                 warmup_steps: int = 0, gamma: float = 1.0):
+        if not warmup_steps < first_cycle_steps:
+            raise ValueError(f"warmup_steps ({warmup_steps}) must be below first_cycle_steps ({first_cycle_steps})")
+        self.optimizer = optimizer
+        self.cycle_mult, self.base_max_lr, self.min_lr, self.warmup_steps, self.gamma = cycle_mult, max_lr, min_lr, warmup_steps, gamma
+        self.cycle_steps, self.cycle, self.t = first_cycle_steps, 0, -1
+        self.step()
+
+    def rate(self):
+        lo, hi = self.min_lr, self.base_max_lr * self.gamma ** self.cycle
+        if self.t < self.warmup_steps:
+            return (hi - lo) * self.t / self.warmup_steps + lo
+        return lo + (hi - lo) * (1 + math.cos(math.pi * (self.t - self.warmup_steps) / (self.cycle_steps - self.warmup_steps))) / 2
+
+    def step(self):
+        self.t += 1
+        if self.t >= self.cycle_steps:
+            self.cycle += 1
+            self.t -= self.cycle_steps
+            self.cycle_steps = int((self.cycle_steps - self.warmup_steps) * self.cycle_mult) + self.warmup_steps
+        lr = self.rate()
+        for group in self.optimizer.param_groups:
+            group["lr"] = lr
+
+
+def load_checkpoint(model, path, device):
+    """trainer.py:67-75: ``model_state_dict`` with ``module.`` prefixes stripped, strict."""
+    checkpoint = torch.load(path, map_location=device)
+    sd = OrderedDict((k[7:] if k.startswith("module.") else k, v) for k, v in checkpoint["model_state_dict"].items())
+    model.load_state_dict(sd)
+    return model
+
+
+def _save(model, path):
+    torch.save({"model_state_dict": model.state_dict()}, path)
+
+
+def _save_best(model, stat, best, path):
+    if stat > best:
+        best = stat
+        _save(model, path)
+        print("Saving ", path)
+    return best
+
+
+def SemanticTraining(args):
+    """``args``: the namespace of ``train.py`` - ``wdir``, ``model``, ``trfile`` / ``tefile`` (voxel directories), ``batch_size``,
+    ``num_epochs``, ``checkpoints``, ``augmentation``, ``test``, ``tune``, ``stop_early``, ``wandb``, ``seed``; ``args.C`` (not on the
+    command line) is the network's width, 32 when absent.  Returns the history array."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("SemanticTraining needs an MI355X (cuda) device; there is no CPU fallback")
+    device = torch.device("cuda")
+    seed = int(getattr(args, "seed", 141190))                   # the reference's module-level torch.manual_seed(141190)
+    torch.manual_seed(seed)
+    wandb = None
+    if args.wandb:
+        try:
+            import wandb
+        except ImportError as e:
+            raise SystemExit("--wandb needs the wandb module, which is not installed here; run without --wandb") from e
+        wandb.init(project="PointsToWood", config={"architecture": "pointnet++", "dataset": "high resolution 2 & 4 m voxels",
+                                                   "epochs": args.num_epochs})
+
+    model = _train.Net(num_classes=1, C=int(getattr(args, "C", 32))).to(device)
+    print("Model contains", sum(p.numel() for p in model.parameters()), " parameters")
+
+    train_feed = TrainingFeed(TrainingSet(args.trfile, device), args.batch_size, shuffle=True, drop_last=True,
+                              augmentation=args.augmentation, mode="train", seed=seed)
+    test_feed = None
+    if args.test:
+        test_feed = TrainingFeed(TrainingSet(args.tefile, device), int(args.batch_size / 2), shuffle=True, drop_last=True,
+                                 augmentation=args.augmentation, mode="test", seed=seed + 1)
+    for name, f in (("training", train_feed), ("test", test_feed)):
+        if f is not None and len(f) == 0:
+            raise ValueError(f"the {name} set has {len(f.set)} voxels: fewer than one batch of {f.batch_size}")
+
+    criterion = Poly1FocalLoss(reduction="mean", gamma=2.0, alpha=None, label_smoothing=0.1)
+    params = [p for p in model.parameters() if p.requires_grad]
+    if args.tune:
+        optimizer = torch.optim.AdamW(params, lr=1e-6, weight_decay=1e-2)
+        lr_scheduler = CosineAnnealingWarmupRestarts(optimizer, first_cycle_steps=args.num_epochs // 5, cycle_mult=1.0, max_lr=1e-6,
+                                                     min_lr=1e-8, warmup_steps=5, gamma=0.5)
+    else:
+        optimizer = torch.optim.AdamW(params, lr=1e-4, weight_decay=1e-2)
+        lr_scheduler = torch.optim.lr_scheduler.OneCycleLR(optimizer, max_lr=1e-4, total_steps=args.num_epochs, pct_start=0.05,
+                                                           anneal_strategy="cos", div_factor=100)
+
+    model_dir = os.path.join(args.wdir, "model")
+    os.makedirs(model_dir, exist_ok=True)
+    model_path = os.path.join(model_dir, args.model)
+    stem = os.path.splitext(args.model)[0]
+    if os.path.isfile(model_path):
+        print("Loading model")
+        try:
+            load_checkpoint(model, model_path, device)
+        except KeyError:
+            print("Failed to load, creating new...")
+            torch.save(model.state_dict(), model_path)
+    else:
+        print("\nModel not found, creating new file...")
+        torch.save(model.state_dict(), model_path)
+
+    def log_history(history):
+        try:
+            np.savetxt(os.path.join(model_dir, stem + "_history.csv"), history)
+            print("Saved training history successfully.")
+        except OSError:
+            np.savetxt(os.path.join(model_dir, stem + "_history_backup.csv"), history)
+
+    best_ba_train = best_f1_train = best_ba_test = best_f1_test = best_precision_test = 0.0
+    scaler = torch.amp.GradScaler("cuda", init_scale=512)
+    history = None
+    consec_decreases = 0
+
+    for epoch in range(1, args.num_epochs + 1):
+        model.train()
+        print("\n=============================================================================================")
+        print("EPOCH ", epoch)
+        train_feed.set_epoch(epoch)
+        scores = EpochScores(capacity=len(train_feed))
+        for data in train_feed:
+            optimizer.zero_grad()
+            with torch.autocast("cuda", dtype=torch.float16):
+                outputs = model(data)
+                loss, _ = criterion(outputs, data.y)
+            scaler.scale(loss).backward()
+            scaler.unscale_(optimizer)
+            torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=1.0)
+            scaler.step(optimizer)
+            scaler.update()
+            scores.add(outputs, data.y, loss)
+        lr_scheduler.step()
+        tr = scores.result()                                    # the epoch's one device-to-host copy
+        lr = optimizer.param_groups[0]["lr"]
+        print(f"Train  Lr {lr:.3g}  Lo {tr['loss']:.5f}  Ac {tr['balanced_accuracy']:.3f}  Pr {tr['precision']:.3f}  "
+              f"Re {tr['recall']:.3f}  F1 {tr['f1']:.3f}")
+
+        te = None
+        if test_feed is not None:
+            model.eval()
+            test_feed.set_epoch(epoch)
+            scores = EpochScores(capacity=len(test_feed))
+            with torch.no_grad():
+                for data in test_feed:
+                    scores.add(model(data), data.y)
+            te = scores.result()
+            print(f"Test   Ac {te['balanced_accuracy']:.3f}  Pr {te['precision']:.3f}  Re {te['recall']:.3f}  F1 {te['f1']:.3f}")
+
+        row = [epoch, lr, tr["loss"], tr["balanced_accuracy"], tr["f1"], tr["precision"], tr["recall"]]
+        if te is not None:
+            row += [te["balanced_accuracy"], te["f1"], te["precision"], te["recall"]]
+        row = np.array([row], dtype=np.float64)
+        history = row if history is None else np.vstack((history, row))
+        log_history(history)
+
+        if epoch in args.checkpoints:
+            folder = os.path.join(args.wdir, "checkpoints")
+            os.makedirs(folder, exist_ok=True)
+            _save(model, os.path.join(folder, f"epoch_{epoch}.pth"))
+
+        if args.stop_early and epoch > 10:
+            consec_decreases = consec_decreases + 1 if history[-1, 3] < history[-2, 3] else 0
+            if consec_decreases >= 10:
+                print(f"\nStopping early at epoch {epoch} - training accuracy decreased for {consec_decreases} consecutive epochs")
+                print(f"Best accuracy was {max(history[:, 3]):.4f} at epoch {np.argmax(history[:, 3]) + 1}")
+                break
+
+        base = os.path.basename(args.model)
+        if epoch > int(args.num_epochs * 0.10) and not args.test:
+            best_ba_train = _save_best(model, tr["balanced_accuracy"], best_ba_train, os.path.join(model_dir, "ba-" + base))
+            best_f1_train = _save_best(model, tr["f1"], best_f1_train, os.path.join(model_dir, "f1-" + base))
+        if args.test and epoch > int(args.num_epochs * 0.5):
+            best_ba_test = _save_best(model, te["balanced_accuracy"], best_ba_test, os.path.join(model_dir, "ba-" + base))
+            best_f1_test = _save_best(model, te["f1"], best_f1_test, os.path.join(model_dir, "f1-" + base))
+            best_precision_test = _save_best(model, te["precision"], best_precision_test, os.path.join(model_dir, "precision-" + base))
+
+        if epoch == args.num_epochs:
+            print("Saving final GLOBAL model")
+            _save(model, model_path)
+
+        if wandb is not None:
+            wandb.log({"Epoch": epoch, "Learning Rate": lr, "Loss": np.around(tr["loss"], 4),
+                       "Accuracy": np.around(tr["balanced_accuracy"], 4), "Precision": np.around(tr["precision"], 4),
+                       "Recall": np.around(tr["recall"], 4), "F1": np.around(tr["f1"], 4),
+                       "Test F1": np.around(te["f1"], 4) if te is not None else 0.0,
+                       "Test Accuracy": np.around(te["balanced_accuracy"], 4) if te is not None else 0.0})
+    return history

@@ -31,6 +31,7 @@ static std::vector<Region> g_regions;
 #include "../pointstowood_amd/csrc/p2w_bnchain.hip"
 #include "../pointstowood_amd/csrc/p2w_fp.hip"
 #include "../pointstowood_amd/csrc/p2w_head.hip"
+#include "../pointstowood_amd/csrc/p2w_feed.hip"
 
 static int g_fail = 0, g_runs = 0;
 
@@ -80,6 +81,7 @@ int main() {
             check("sssp_carve", n, t, 0, [&](P2wArena& a) { sssp_carve(a, n, t); });
         }
         for (int N : {1, 64, 65, 256}) check("rowdot_carve", n, N, 0, [&](P2wArena& a) { rowdot_carve(a, i, N); });
+        for (int B : {0, 1, 3, 257}) check("fd_carve", n, B, 0, [&](P2wArena& a) { fd_carve(a, n, B); });
         for (int s : {1, 3, 7})
             for (int c : {2, 3, 8}) check("ev_carve", n, s, c, [&](P2wArena& a) { ev_carve(a, n, s, c); });
         for (int rows : {0, 1, 2, 257}) {

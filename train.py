@@ -1,0 +1,128 @@
+#!/usr/bin/env python3
+"""train.py - the training command line of the MI355X build, with the reference's flags (``pointstowood/train.py:60-76``).
+
+    python train.py --wdir DIR [--preprocess] [--test] [--augmentation] --num_epochs 300 --batch_size 8 --model model.pth
+
+``DIR`` holds what the reference keeps in its ``pointstowood`` folder: ``data/train/voxels/*.pt`` and ``data/test/voxels/*.pt`` (float32
+``[n, >= 5]`` = x, y, z, reflectance, label, ...; written by ``--preprocess`` from ``data/train/*.ply`` and ``data/test/*.ply``),
+``model/`` (the model, its ``_history.csv`` and the ``ba-`` / ``f1-`` / ``precision-`` best models) and ``checkpoints/``.  The reference
+finds that folder by searching its own checkout's name in the working directory; here it is ``--wdir`` (default: the working
+directory).  ``--seed`` seeds the initialisation, the network's training sample and the feed (default: the reference's 141190).
+
+The loop is ``pointstowood_amd.trainer.SemanticTraining``: the whole set lives on the GPU, and every batch is gathered, augmented,
+centred and collated there (``pointstowood_amd.feed``).
+"""
+from __future__ import annotations
+
+import argparse
+import glob
+import os
+import shutil
+
+import numpy as np
+
+
+def build_parser():
+    p = argparse.ArgumentParser()
+    p.add_argument('--device', type=str, default='cuda', help='Insert either "cuda" or "cpu" (only cuda is built: there is no CPU path)')
+    p.add_argument('--num_procs', type=int, default=1, help='Number of cpu cores to use')
+    p.add_argument('--num_epochs', default=2, type=int, metavar='N', help='number of total epochs to run')
+    p.add_argument('--checkpoint_saves', default=1, type=int, metavar='N', help='number of times to save model')
+    p.add_argument('--model', type=str, default='model.pth', help='Name of global model [e.g. model.pth]')
+    p.add_argument('--resolution', type=float, default=0.01, help='Resolution to which point cloud is downsampled [m]')
+    p.add_argument('--grid_size', type=float, nargs='+', default=[2.0, 4.0], help='Grid sizes for voxelization')
+    p.add_argument('--min_pts', type=int, default=8192, help='Minimum number of points in voxel')
+    p.add_argument('--max_pts', type=int, default=16384, help='Maximum number of points in voxel')
+    p.add_argument('--batch_size', type=int, default=2, help='Batch size for cuda processing [Lower less memory usage]')
+    p.add_argument('--augmentation', action='store_true', help="Perform data augmentation")
+    p.add_argument('--preprocess', action='store_true', help="Preprocess point clouds into voxels")
+    p.add_argument('--test', action='store_true', help="Perform model testing during training")
+    p.add_argument('--tune', action='store_true', help="Tune model hyperparameters with lower learning rate schedule")
+    p.add_argument('--stop_early', action='store_true', help="Break training run if training accuracy continually decreases")
+    p.add_argument('--wandb', action='store_true', help="Use wandb for logging")
+    p.add_argument('--verbose', action='store_true', help="print stuff")
+    # extensions of this build
+    p.add_argument('--wdir', type=str, default=os.getcwd(), help='working directory with data/, model/ and checkpoints/')
+    p.add_argument('--seed', type=int, default=141190, help='seed of the initialisation, the sampling and the feed')
+    return p
+
+
+def training_columns(columns):
+    """``preprocess_point_cloud_data`` of the reference's train.py (:36-49) over ``io.prepare_columns``: the label (a ``truth`` or
+    ``label`` column, ``scalar_`` prefix or not) is kept and placed at column 4, behind x, y, z, reflectance - where the training set
+    reads it.  -> (names, [n, cols] float32 array, had_reflectance)."""
+    from pointstowood_amd import io as pio
+    label = None
+    rest = {}
+    for name, v in columns.items():
+        if name.lower().replace("scalar_", "") in ("truth", "label"):
+            label = v
+        else:
+            rest[name] = v
+    if label is None:
+        raise SystemExit("no 'truth' or 'label' column: a training cloud needs one")
+    cols, _, had = pio.prepare_columns(rest)
+    names = list(cols)
+    names.insert(4, "label")
+    cols["label"] = label
+    xyz = np.stack([np.asarray(cols[c], dtype=np.float64) for c in names[:3]], 1)
+    xyz -= xyz.min(0)                                           # plot-local coordinates: fp32 keeps millimetres at any easting
+    arr = np.concatenate([xyz] + [np.asarray(cols[c], dtype=np.float64)[:, None] for c in names[3:]], 1)
+    return names, arr.astype(np.float32), had
+
+
+def preprocess(files, out_dir, args):
+    """Every PLY of ``files`` through the voxeliser into ``out_dir/voxel_<i>.pt`` (float32 [n, >= 5] CPU tensors)."""
+    import torch
+    from pointstowood_amd import io as pio
+    from pointstowood_amd.preprocessing import voxelise
+    if os.path.exists(out_dir):
+        shutil.rmtree(out_dir)
+    os.makedirs(out_dir, exist_ok=True)
+    count = 0
+    for path in files:
+        names, arr, had = training_columns(pio.read_ply(path))
+        print('Reflectance detected' if had else 'No reflectance detected, column added with zeros.')
+        print(f'Voxelising {path} to {args.grid_size} grid sizes')
+        voxels, _ = voxelise(torch.from_numpy(arr).to('cuda'), args.grid_size, args.min_pts, args.max_pts, ground='n_z' not in names)
+        for v in voxels:
+            torch.save(v.cpu().clone(), os.path.join(out_dir, f'voxel_{count}.pt'))
+            count += 1
+    return count
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    import torch
+    if args.device != 'cuda' or not torch.cuda.is_available():
+        raise SystemExit('train.py needs an MI355X: the HIP path has no CPU fallback')
+    torch.set_num_threads(max(1, args.num_procs))
+    args.wdir = os.path.abspath(args.wdir)
+    args.mode = 'train'
+    print('Mode: {}'.format(args.mode))
+
+    # checkpointing, as the reference organises it (train.py:88-94): the old checkpoints are archived, then removed
+    args.checkpoints = np.arange(0, args.num_epochs + 1, max(1, int(args.num_epochs / args.checkpoint_saves)))
+    old = glob.glob(os.path.join(args.wdir, 'checkpoints', '*.pth'))
+    if old:
+        shutil.make_archive(os.path.join(args.wdir, 'checkpoints_backup'), 'zip', os.path.join(args.wdir, 'checkpoints'))
+    for f in old:
+        os.remove(f)
+
+    args.trfile = os.path.join(args.wdir, 'data', 'train', 'voxels')
+    args.tefile = os.path.join(args.wdir, 'data', 'test', 'voxels')
+    if args.preprocess:
+        n = preprocess(sorted(glob.glob(os.path.join(args.wdir, 'data', 'train', '*.ply'))), args.trfile, args)
+        print(f'{n} training voxels')
+        if args.test:
+            n = preprocess(sorted(glob.glob(os.path.join(args.wdir, 'data', 'test', '*.ply'))), args.tefile, args)
+            print(f'{n} test voxels')
+    if args.augmentation:
+        print('Training with data augmentation performed on 25% of samples')
+
+    from pointstowood_amd.trainer import SemanticTraining
+    return SemanticTraining(args)
+
+
+if __name__ == '__main__':
+    main()
