@@ -42,6 +42,7 @@ EDGE_CHUNK = 1024                                                               
 BN_GROUP = 16                                                                                      # P2W_BN_GROUP
 BN_CHAIN_MAX, BN_CHAIN_ROWS = 3, 32                                                                # P2W_BN_CHAIN_*
 FEED_CHUNK, FEED_STREAM = 256, 0x50325746                                                          # P2W_FEED_*
+F32, F16 = 0, 1                                                                                    # P2W_F32, P2W_F16
 
 SIGNATURES = {
     "p2w_version": (_i32, []),
@@ -146,6 +147,18 @@ SIGNATURES = {
     "p2w_bn_relu_rowdot_ws_size": (_sz, [_i32, _i32]),
     "p2w_bn_relu_rowdot": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "p2w_bn_relu_rowdot_bwd": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "p2w_bn_chain_io": (_i32, [_vp, _i32, _i32, _vp, _i32, C.POINTER(BnStage), _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "p2w_bn_chain_bwd_io": (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, C.POINTER(BnStage), _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp,
+                                   _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "p2w_relu_bn_io": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _sz,
+                              _vp]),
+    "p2w_relu_bn_bwd_io": (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "p2w_bn_relu_rowdot_io": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _i32, _i32, _vp, _vp, _vp, _vp,
+                                     _sz, _vp]),
+    "p2w_bn_relu_rowdot_bwd_io": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz,
+                                         _vp]),
+    "p2w_segment_max_arg_io": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "p2w_segment_max_bwd_io": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
 }
 
 _lib = None

@@ -81,9 +81,10 @@ template <int V> __device__ __forceinline__ void bc_pre(float (&x)[V]) {
     const int c = (int)(gid % q) * V;                                          \
     const int r0 = item * BC_R, r1 = min(M, r0 + BC_R)
 
-// Forward, statistics of stage S + 1 (S = the stages in front of it, recomputed): s1 = sum u_S, s2 = sum u_S^2 per item and column
-template <int V, int S, bool PRE = false>
-__global__ __launch_bounds__(256) void bc_stats_kernel(BcParams P, const float* __restrict__ z, int ldz, int M, int C, int q, int items,
+// Forward, statistics of stage S + 1 (S = the stages in front of it, recomputed): s1 = sum u_S, s2 = sum u_S^2 per item and column.
+// TZ = the element type of z (float, or gr_half widened as it is loaded)
+template <int V, int S, bool PRE = false, class TZ = float>
+__global__ __launch_bounds__(256) void bc_stats_kernel(BcParams P, const TZ* __restrict__ z, int ldz, int M, int C, int q, int items,
                                                        double* __restrict__ part) {
     BC_ITEM_PROLOGUE();
     BcCol<V> k[S > 0 ? S : 1];

@@ -7,7 +7,11 @@
 // slot order after a stable sort, in a tree whose shape depends only on the sizes.
 // All kernels are bandwidth-bound: one wave covers 256 consecutive columns of a row with 16-byte accesses where rows and pointers
 // allow it (V = 4), and falls back to 4-byte accesses (V = 1, still coalesced) for odd widths.
+// The segment max also takes a float16 x and writes a float16 grad_x (p2w_segment_max_arg_io / _bwd_io; TX = gr_half, p2w_runsum.h):
+// values are widened as they are loaded - a maximum of widened values is exact, so out stays fp32 - and the gathered gradient is
+// rounded to nearest even as it is stored; V = 4 is then an 8-byte access.
 #include "p2w_runsum.h"
+#include "p2w_segmax.h"
 
 namespace {
 
@@ -25,8 +29,8 @@ __device__ __forceinline__ float gr_ord2f(unsigned o) {
 // r, r + 4, ... and are combined in LDS; value and winner are written directly.  A NaN takes no part (fmaxf in p2w_segment_max
 // ignores it too); the value is the maximum by the order key (the bits p2w_segment_max's atomicMax leaves), the winner the
 // lowest row that compares equal to it.
-template <int V>
-__global__ __launch_bounds__(256) void segmax_arg_kernel(const float* __restrict__ x, int ldx, int F, const int* __restrict__ ptr, int ncg,
+template <int V, class TX>
+__global__ __launch_bounds__(256) void segmax_arg_kernel(const TX* __restrict__ x, int ldx, int F, const int* __restrict__ ptr, int ncg,
                                                          float* __restrict__ out, int* __restrict__ arg) {
     __shared__ float sv[3][64 * V];
     __shared__ unsigned so[3][64 * V];
@@ -77,8 +81,8 @@ __global__ __launch_bounds__(256) void segmax_arg_kernel(const float* __restrict
 // Few segments (global_max_pool): p2w_segment_max itself gives the values (rows split over 16 blocks per segment, integer
 // atomicMax); this kernel then finds the lowest row that equals the value, split the same way, with an integer atomicMax of
 // 0xffffffff - row into `arg` (pre-set to 0, which decodes to -1 = no row).
-template <int V>
-__global__ __launch_bounds__(256) void segmax_argonly_kernel(const float* __restrict__ x, int ldx, int F, const int* __restrict__ ptr,
+template <int V, class TX>
+__global__ __launch_bounds__(256) void segmax_argonly_kernel(const TX* __restrict__ x, int ldx, int F, const int* __restrict__ ptr,
                                                              const float* __restrict__ out, unsigned* __restrict__ arg) {
     __shared__ unsigned sk[3][64 * V];
     const int b = blockIdx.y;
@@ -120,9 +124,9 @@ __global__ __launch_bounds__(256) void segmax_arg_decode_kernel(unsigned* __rest
 }
 
 // grad_x[r, c] = arg[b(r), c] == r ? grad_out[b(r), c] : 0: one thread per (row, V columns), every element written once.
-template <int V>
+template <int V, class TX>
 __global__ __launch_bounds__(256) void segmax_bwd_kernel(const float* __restrict__ grad_out, int ldg, const int* __restrict__ arg,
-                                                         const int* __restrict__ ptr, int B, int F, float* __restrict__ grad_x, int ldx,
+                                                         const int* __restrict__ ptr, int B, int F, TX* __restrict__ grad_x, int ldx,
                                                          int n, int q) {
     const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
     if (g >= (long long)n * q) return;
@@ -203,42 +207,79 @@ inline IbWs ib_carve(P2wArena& a, long long N, int n_coarse) {
 
 }  // namespace
 
-extern "C" int32_t p2w_segment_max_arg(const float* x, int32_t ldx, int32_t F, const int32_t* ptr, int32_t B, float* out, int32_t* arg,
-                                       p2w_stream_t stream) {
+namespace {
+
+// the values of the few-segment route, by x's element type
+inline int32_t segmax_values(const float* x, int32_t ldx, int32_t F, const int32_t* ptr, int32_t B, float* out, p2w_stream_t stream) {
+    return p2w_segment_max(x, ldx, F, ptr, B, out, stream);
+}
+inline int32_t segmax_values(const gr_half* x, int32_t ldx, int32_t F, const int32_t* ptr, int32_t B, float* out, p2w_stream_t stream) {
+    return segment_max_launch(x, ldx, F, ptr, B, out, p2w_s(stream));      // p2w_segment_max's kernels on the float16 element type
+}
+
+template <class TX>
+int32_t segmax_arg_t(const TX* x, int32_t ldx, int32_t F, const int32_t* ptr, int32_t B, float* out, int32_t* arg, p2w_stream_t stream) {
     P2W_CHECK_PTR(x); P2W_CHECK_PTR(ptr); P2W_CHECK_PTR(out); P2W_CHECK_PTR(arg);
     if (B <= 0 || F <= 0 || ldx < F) return P2W_EINVAL;
     hipStream_t s = p2w_s(stream);
-    const bool v4 = !(F & 3) && !(ldx & 3) && gr_al16(x) && gr_al16(out) && gr_al16(arg);
+    const bool v4 = !(F & 3) && !(ldx & 3) && gr_alv(x) && gr_al16(out) && gr_al16(arg);
     const int ncg = p2w_cdiv(F, v4 ? 256 : 64);
     if ((long long)B * ncg >= 256) {
         if ((long long)B * ncg > 0x7fffffffll) return P2W_EINVAL;
-        if (v4) segmax_arg_kernel<4><<<B * ncg, 256, 0, s>>>(x, ldx, F, ptr, ncg, out, arg);
-        else segmax_arg_kernel<1><<<B * ncg, 256, 0, s>>>(x, ldx, F, ptr, ncg, out, arg);
+        if (v4) segmax_arg_kernel<4, TX><<<B * ncg, 256, 0, s>>>(x, ldx, F, ptr, ncg, out, arg);
+        else segmax_arg_kernel<1, TX><<<B * ncg, 256, 0, s>>>(x, ldx, F, ptr, ncg, out, arg);
         return P2W_LAUNCH_STATUS();
     }
-    const int32_t st = p2w_segment_max(x, ldx, F, ptr, B, out, stream);
+    const int32_t st = segmax_values(x, ldx, F, ptr, B, out, stream);
     if (st != P2W_OK) return st;
     hipError_t e = hipMemsetAsync(arg, 0, sizeof(int32_t) * (size_t)B * F, s);
     if (e != hipSuccess) return (int32_t)e;
     auto* ua = reinterpret_cast<unsigned*>(arg);
-    if (v4) segmax_argonly_kernel<4><<<dim3(ncg, B, 16), 256, 0, s>>>(x, ldx, F, ptr, out, ua);
-    else segmax_argonly_kernel<1><<<dim3(ncg, B, 16), 256, 0, s>>>(x, ldx, F, ptr, out, ua);
+    if (v4) segmax_argonly_kernel<4, TX><<<dim3(ncg, B, 16), 256, 0, s>>>(x, ldx, F, ptr, out, ua);
+    else segmax_argonly_kernel<1, TX><<<dim3(ncg, B, 16), 256, 0, s>>>(x, ldx, F, ptr, out, ua);
     segmax_arg_decode_kernel<<<p2w_cdiv((long)B * F, 256), 256, 0, s>>>(ua, (long long)B * F);
     return P2W_LAUNCH_STATUS();
 }
 
-extern "C" int32_t p2w_segment_max_bwd(const float* grad_out, int32_t ldg, const int32_t* arg, const int32_t* ptr, int32_t B, int32_t F,
-                                       float* grad_x, int32_t ldx, int32_t n, p2w_stream_t stream) {
+template <class TX>
+int32_t segmax_bwd_t(const float* grad_out, int32_t ldg, const int32_t* arg, const int32_t* ptr, int32_t B, int32_t F, TX* grad_x, int32_t ldx,
+                     int32_t n, p2w_stream_t stream) {
     P2W_CHECK_PTR(grad_out); P2W_CHECK_PTR(arg); P2W_CHECK_PTR(ptr); P2W_CHECK_PTR(grad_x);
     if (B <= 0 || F <= 0 || ldg < F || ldx < F || n < 0) return P2W_EINVAL;
     if (n == 0) return P2W_OK;
-    const bool v4 = !(F & 3) && !(ldg & 3) && !(ldx & 3) && gr_al16(grad_out) && gr_al16(arg) && gr_al16(grad_x);
+    const bool v4 = !(F & 3) && !(ldg & 3) && !(ldx & 3) && gr_al16(grad_out) && gr_al16(arg) && gr_alv(grad_x);
     const int q = v4 ? F >> 2 : F;
     const long long blocks = ((long long)n * q + 255) / 256;
     if (blocks > 0x7fffffffll) return P2W_EINVAL;
-    if (v4) segmax_bwd_kernel<4><<<(unsigned)blocks, 256, 0, p2w_s(stream)>>>(grad_out, ldg, arg, ptr, B, F, grad_x, ldx, n, q);
-    else segmax_bwd_kernel<1><<<(unsigned)blocks, 256, 0, p2w_s(stream)>>>(grad_out, ldg, arg, ptr, B, F, grad_x, ldx, n, q);
+    if (v4) segmax_bwd_kernel<4, TX><<<(unsigned)blocks, 256, 0, p2w_s(stream)>>>(grad_out, ldg, arg, ptr, B, F, grad_x, ldx, n, q);
+    else segmax_bwd_kernel<1, TX><<<(unsigned)blocks, 256, 0, p2w_s(stream)>>>(grad_out, ldg, arg, ptr, B, F, grad_x, ldx, n, q);
     return P2W_LAUNCH_STATUS();
+}
+
+}  // namespace
+
+extern "C" int32_t p2w_segment_max_arg_io(const void* x, int32_t tx, int32_t ldx, int32_t F, const int32_t* ptr, int32_t B, float* out,
+                                          int32_t* arg, p2w_stream_t stream) {
+    if (tx == P2W_F32) return segmax_arg_t(static_cast<const float*>(x), ldx, F, ptr, B, out, arg, stream);
+    if (tx == P2W_F16) return segmax_arg_t(static_cast<const gr_half*>(x), ldx, F, ptr, B, out, arg, stream);
+    return P2W_EUNSUPPORTED;
+}
+
+extern "C" int32_t p2w_segment_max_arg(const float* x, int32_t ldx, int32_t F, const int32_t* ptr, int32_t B, float* out, int32_t* arg,
+                                       p2w_stream_t stream) {
+    return p2w_segment_max_arg_io(x, P2W_F32, ldx, F, ptr, B, out, arg, stream);
+}
+
+extern "C" int32_t p2w_segment_max_bwd_io(const float* grad_out, int32_t ldg, const int32_t* arg, const int32_t* ptr, int32_t B, int32_t F,
+                                          void* grad_x, int32_t tx, int32_t ldx, int32_t n, p2w_stream_t stream) {
+    if (tx == P2W_F32) return segmax_bwd_t(grad_out, ldg, arg, ptr, B, F, static_cast<float*>(grad_x), ldx, n, stream);
+    if (tx == P2W_F16) return segmax_bwd_t(grad_out, ldg, arg, ptr, B, F, static_cast<gr_half*>(grad_x), ldx, n, stream);
+    return P2W_EUNSUPPORTED;
+}
+
+extern "C" int32_t p2w_segment_max_bwd(const float* grad_out, int32_t ldg, const int32_t* arg, const int32_t* ptr, int32_t B, int32_t F,
+                                       float* grad_x, int32_t ldx, int32_t n, p2w_stream_t stream) {
+    return p2w_segment_max_bwd_io(grad_out, ldg, arg, ptr, B, F, grad_x, P2W_F32, ldx, n, stream);
 }
 
 extern "C" size_t p2w_interp_bwd_ws_bytes(int32_t m, int32_t kw, int32_t n_coarse) {

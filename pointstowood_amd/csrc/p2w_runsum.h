@@ -26,6 +26,35 @@ template <int V> __device__ __forceinline__ void gr_st(int* p, const int (&v)[V]
 }
 inline bool gr_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// float16 rows (P2W_F16): the arithmetic stays fp32, only the element type at the loads and stores differs.  A lane keeps its V
+// columns: V = 4 is one 8-byte access.  The widening load is exact (subnormals included).  EVERY fp16 store goes through gr_f2h:
+// one conversion per element, round to nearest even, overflow to +-inf, gradual underflow to subnormals and +-0, a NaN stays a
+// NaN - what torch.Tensor.half() gives.  (The packed conversion that rounds toward zero must not be used.)
+typedef _Float16 gr_half;
+typedef _Float16 gr_half4 __attribute__((ext_vector_type(4)));
+// med3(f, f, f) = f (a NaN stays a NaN, -0 stays -0) keeps the fp32 value apart from the conversion: left alone, the compiler folds
+// the conversion into the multiply that produced the value as one mixed-precision FMA with a +0 addend (v_fma_mixlo_f16 a, b, 0) -
+// one rounding where the fp32 route has two, and +0 where the product is -0.  One v_med3_f32 per stored element in kernels that
+// wait for memory; an empty asm statement would cost nothing, but inline asm is convergent and the row loops are then not unrolled.
+__device__ __forceinline__ gr_half gr_f2h(float f) {
+    return static_cast<gr_half>(__builtin_amdgcn_fmed3f(f, f, f));
+}
+template <int V> __device__ __forceinline__ void gr_ld(const gr_half* p, float (&v)[V]) {
+    if constexpr (V == 4) {
+        const gr_half4 t = *reinterpret_cast<const gr_half4*>(p);
+        v[0] = (float)t.x; v[1] = (float)t.y; v[2] = (float)t.z; v[3] = (float)t.w;
+    } else v[0] = (float)*p;
+}
+template <int V> __device__ __forceinline__ void gr_st(gr_half* p, const float (&v)[V]) {
+    if constexpr (V == 4) {
+        gr_half4 t;
+        t.x = gr_f2h(v[0]); t.y = gr_f2h(v[1]); t.z = gr_f2h(v[2]); t.w = gr_f2h(v[3]);
+        *reinterpret_cast<gr_half4*>(p) = t;
+    } else *p = gr_f2h(v[0]);
+}
+// a V = 4 access of element type T needs 4 sizeof(T) bytes of alignment: 16 for fp32, 8 for fp16
+template <class T> inline bool gr_alv(const T* p) { return (reinterpret_cast<uintptr_t>(p) & (4 * sizeof(T) - 1)) == 0; }
+
 constexpr int RUN_SPLIT_MIN = 512;    // mean run length from which the runs are split over blocks
 constexpr int RUN_SPLIT_LEN = 256;    // ... into pieces of about this many slots
 constexpr int RUN_SPLIT_MAX = 64;

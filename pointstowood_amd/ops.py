@@ -28,6 +28,10 @@ fused eval-mode kernel and ``Net.forward`` stay inference-only.  ``InvertedResid
 BatchNorm1d, ReLU, up to three times, and the residual add - computed from the GEMM's output alone in both directions.  ``FPModule``
 (``model.py:142-153``) trains through ``interp_add_relu`` (``csrc/p2w_fp.hip``: layer 0 hoisted behind the interpolation, the add and the
 ReLU in the interpolation's pass) and ``relu_bn`` (``csrc/p2w_bnchain.hip``: ReLU and training-mode BatchNorm1d from the GEMM's output).
+
+dtypes under autocast: ``bn_chain``, ``relu_bn``, ``bn_relu_rowdot`` and ``scatter_max`` / ``global_max_pool`` take a float16 tensor as it is,
+save that tensor and write a float16 gradient from the kernel (``half_io``, default True; False casts to fp32 first - the same bits);
+``bn_chain`` and ``relu_bn`` return float16 on request (``out_dtype``), for a result that goes into ``F.linear`` and nowhere else.
 """
 from __future__ import annotations
 
@@ -139,6 +143,34 @@ def _wants_grad(x):
     return torch.is_grad_enabled() and x.requires_grad
 
 
+# float16 in and out of the training operators.  Under autocast the GEMMs around bn_chain, relu_bn, bn_relu_rowdot and scatter_max /
+# global_max_pool give and take float16.  True: with a gradient to track, a float16 z / x goes to the kernels as it is (the ``*_io``
+# entry points of include/p2w.h widen it as they load it), it is the tensor saved for the backward, and dz / grad_x is written in
+# float16 by the kernel.  False: the route as it was - the big tensor is cast to fp32 first, that copy is saved, and the fp32
+# gradient is rounded in one more pass - launch for launch.  The two give the same bits everywhere: only the element type at the
+# loads and stores differs, and a float16 store is the one rounding the cast would have made.
+half_io = True
+
+
+def _keeps_half(x):
+    return half_io and x.dtype == torch.float16 and x.is_cuda
+
+
+def _code(t):
+    return _lib.F16 if t.dtype == torch.float16 else _lib.F32
+
+
+def _grad_for(grad_out, z):
+    """The output's gradient as the kernel reads it: float16 as it arrives where z is float16, fp32 otherwise."""
+    if z.dtype == torch.float16 and grad_out.dtype == torch.float16:
+        return grad_out.contiguous()
+    return _f32c(grad_out)
+
+
+def _no_autocast():
+    return torch.autocast("cuda", enabled=False)
+
+
 def _pad4(x):
     """fp32, contiguous, rows padded to a multiple of 4 floats (the interpolation kernels' 16-byte accesses)."""
     F0 = x.shape[1]
@@ -154,27 +186,49 @@ class _SegmentMax(torch.autograd.Function):
     (``p2w_segment_max_bwd``).  The arg table is saved for backward only."""
 
     @staticmethod
-    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, x, csr, nb):
-        xc = x.to(torch.float32).contiguous()
+    def _forward(ctx, x, csr, nb, keeps_half=False):
+        xc = x.contiguous() if keeps_half else x.to(torch.float32).contiguous()
         n, F = xc.shape
         out = torch.empty((nb, F), dtype=torch.float32, device=x.device)
         arg = torch.empty((nb, F), dtype=torch.int32, device=x.device)
-        check(lib().p2w_segment_max_arg(ptr(xc), F, F, ptr(csr), nb, ptr(out), ptr(arg), stream()), "segment_max_arg")
+        check(lib().p2w_segment_max_arg_io(ptr(xc), _code(xc), F, F, ptr(csr), nb, ptr(out), ptr(arg), stream()), "segment_max_arg")
         ctx.save_for_backward(arg, csr)
-        ctx.shape, ctx.dtype = (n, F), x.dtype
+        ctx.shape, ctx.dtype, ctx.kernel_dtype = (n, F), x.dtype, xc.dtype
         return out
+
+    @staticmethod
+    def _backward(ctx, grad_out):
+        arg, csr = ctx.saved_tensors
+        n, F = ctx.shape
+        g = grad_out.to(torch.float32).contiguous()
+        grad_x = torch.empty((n, F), dtype=ctx.kernel_dtype, device=g.device)
+        check(lib().p2w_segment_max_bwd_io(ptr(g), F, ptr(arg), ptr(csr), arg.shape[0], F, ptr(grad_x), _code(grad_x), F, n, stream()),
+              "segment_max_bwd")
+        return grad_x.to(ctx.dtype), None, None
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, x, csr, nb):
+        return _SegmentMax._forward(ctx, x, csr, nb)
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_out):
-        arg, csr = ctx.saved_tensors
-        n, F = ctx.shape
-        g = grad_out.to(torch.float32).contiguous()
-        grad_x = torch.empty((n, F), dtype=torch.float32, device=g.device)
-        check(lib().p2w_segment_max_bwd(ptr(g), F, ptr(arg), ptr(csr), arg.shape[0], F, ptr(grad_x), F, n, stream()),
-              "segment_max_bwd")
-        return grad_x.to(ctx.dtype), None, None
+        return _SegmentMax._backward(ctx, grad_out)
+
+
+class _SegmentMaxHalf(_SegmentMax):
+    """``_SegmentMax`` on a float16 ``x`` as it is (``half_io``): no fp32 copy of ``x``, ``grad_x`` written in float16 by the kernel."""
+
+    @staticmethod
+    def forward(ctx, x, csr, nb):
+        with _no_autocast():
+            return _SegmentMax._forward(ctx, x, csr, nb, keeps_half=True)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        with _no_autocast():
+            return _SegmentMax._backward(ctx, grad_out)
 
 
 def global_max_pool(x, batch, size=None):
@@ -187,7 +241,7 @@ def global_max_pool(x, batch, size=None):
     nb = _num_batches(batch) if size is None else int(size)
     csr = _csr(batch, nb)
     if _wants_grad(x):
-        return _SegmentMax.apply(x, csr, nb)
+        return (_SegmentMaxHalf if _keeps_half(x) else _SegmentMax).apply(x, csr, nb)
     x = x.to(torch.float32).contiguous()
     out = torch.empty((nb, x.shape[1]), dtype=torch.float32, device=x.device)
     check(lib().p2w_segment_max(ptr(x), x.shape[1], x.shape[1], ptr(csr), nb, ptr(out), stream()), "global_max_pool")
@@ -619,15 +673,16 @@ def _chain_ws(M, C, L, dev):
     return torch.empty(need, dtype=torch.uint8, device=dev)
 
 
-def _bn_chain_forward(zc, rc, meta, vec):
-    """(out, mean, invstd) of ``p2w_bn_chain`` on fp32, contiguous inputs; every bn's running statistics move in place."""
+def _bn_chain_forward(zc, rc, meta, vec, out_dtype=torch.float32):
+    """(out, mean, invstd) of ``p2w_bn_chain_io`` on a contiguous fp32 or float16 z (everything else fp32, contiguous); every bn's
+    running statistics move in place."""
     (M, C), L, dev = zc.shape, len(meta), zc.device
-    out = torch.empty((M, C), dtype=torch.float32, device=dev)
+    out = torch.empty((M, C), dtype=out_dtype, device=dev)
     mean, invstd = (torch.empty((L, C), dtype=torch.float32, device=dev) for _ in range(2))
     running = [tuple(t.detach().to(torch.float32).contiguous() for t in (bn.running_mean, bn.running_var)) for bn, _, _ in meta]
     ws = _chain_ws(M, C, L, dev)
-    check(lib().p2w_bn_chain(ptr(zc), C, ptr(rc), C, _chain_stage_array(meta, vec, running), L, M, C, ptr(out), C, ptr(mean), ptr(invstd),
-                             ptr(ws), ws.numel(), stream()), "bn_chain")
+    check(lib().p2w_bn_chain_io(ptr(zc), _code(zc), C, ptr(rc), C, _chain_stage_array(meta, vec, running), L, M, C, ptr(out), _code(out), C,
+                                ptr(mean), ptr(invstd), ptr(ws), ws.numel(), stream()), "bn_chain")
     with torch.no_grad():
         for (bn, _, _), (rm, rv) in zip(meta, running):
             for mine, theirs in ((rm, bn.running_mean), (rv, bn.running_var)):
@@ -643,41 +698,66 @@ class _BnChain(torch.autograd.Function):
     to a depthwise bias is exactly zero: BatchNorm subtracts the column mean, which removes any bias added in front of it."""
 
     @staticmethod
-    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, z, residual, meta, *params):          # (meta holds modules and flags, no tensors: custom_fwd passes it through)
-        zc = _f32c(z)
+    def _forward(ctx, z, residual, meta, params, out_dtype=torch.float32, keeps_half=False):
+        zc = z.detach().contiguous() if keeps_half else _f32c(z)
         rc = None if residual is None else _f32c(residual)
         vec = [_f32c(p.reshape(-1)) for p in params]
-        out, mean, invstd = _bn_chain_forward(zc, rc, meta, vec)
+        out, mean, invstd = _bn_chain_forward(zc, rc, meta, vec, out_dtype)
         ctx.save_for_backward(zc, mean, invstd, *vec, *([out] if rc is not None else []))
         ctx.meta, ctx.has_res = meta, rc is not None
         ctx.like = [(t.dtype, t.shape) for t in (z, *params)] + ([(residual.dtype, residual.shape)] if rc is not None else [])
         return out
 
     @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, z, residual, meta, *params):          # (meta holds modules and flags, no tensors: custom_fwd passes it through)
+        return _BnChain._forward(ctx, z, residual, meta, params)
+
+    @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_out):
+        return _BnChain._backward(ctx, grad_out)
+
+    @staticmethod
+    def _backward(ctx, grad_out):
         saved = ctx.saved_tensors
         z, mean, invstd = saved[:3]
         meta, n_vec = ctx.meta, sum(4 if m[2] else 2 for m in ctx.meta)
         vec, out = saved[3:3 + n_vec], (saved[3 + n_vec] if ctx.has_res else None)
         (M, C), L, dev = z.shape, len(meta), z.device
-        g = _f32c(grad_out)
-        dz = torch.empty((M, C), dtype=torch.float32, device=dev)
+        g = _grad_for(grad_out, z)
+        dz = torch.empty((M, C), dtype=z.dtype, device=dev)
         dres = torch.empty((M, C), dtype=torch.float32, device=dev) if ctx.has_res and ctx.needs_input_grad[1] else None
         dgamma, dbeta = (torch.empty((L, C), dtype=torch.float32, device=dev) for _ in range(2))
         any_dw = any(m[2] for m in meta)
         ddw_w, ddw_b = (torch.empty((L, C), dtype=torch.float32, device=dev) for _ in range(2)) if any_dw else (None, None)
         ws = _chain_ws(M, C, L, dev)
-        check(lib().p2w_bn_chain_bwd(ptr(g), C, ptr(z), C, ptr(out), C, _chain_stage_array(meta, vec, None), L, ptr(mean), ptr(invstd), M, C,
-                                     ptr(dz), C, ptr(dres), C, ptr(dgamma), ptr(dbeta), ptr(ddw_w), ptr(ddw_b), ptr(ws), ws.numel(), stream()),
-              "bn_chain backward")
+        check(lib().p2w_bn_chain_bwd_io(ptr(g), _code(g), C, ptr(z), _code(z), C, ptr(out), C, _chain_stage_array(meta, vec, None), L, ptr(mean),
+                                        ptr(invstd), M, C, ptr(dz), C, ptr(dres), C, ptr(dgamma), ptr(dbeta), ptr(ddw_w), ptr(ddw_b), ptr(ws),
+                                        ws.numel(), stream()), "bn_chain backward")
         grads = []
         for t, (_, _, has_dw) in enumerate(meta):
             grads += [dgamma[t], dbeta[t]] + ([ddw_w[t], ddw_b[t]] if has_dw else [])
         like = ctx.like
         grads = [gr.to(dt).reshape(shape) for gr, (dt, shape) in zip(grads, like[1:1 + n_vec])]
         return (dz.to(like[0][0]), None if dres is None else dres.to(like[-1][0]), None, *grads)
+
+
+class _BnChainHalf(_BnChain):
+    """``_BnChain`` on a float16 ``z`` as it is (``half_io``): ``z`` itself is saved, the output is fp32 or float16, its gradient is read in
+    the dtype it arrives in and ``dz`` is written in float16 by the kernel.  Parameters, the residual and the saved output of a chain
+    with a residual stay fp32."""
+
+    @staticmethod
+    def forward(ctx, z, residual, meta, out_dtype, *params):
+        with _no_autocast():
+            return _BnChain._forward(ctx, z, residual, meta, params, out_dtype, keeps_half=True)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        with _no_autocast():
+            grads = _BnChain._backward(ctx, grad_out)
+        return (*grads[:3], None, *grads[3:])
 
 
 def _chain_normalise(stages, C, who="bn_chain"):
@@ -700,7 +780,15 @@ def _chain_normalise(stages, C, who="bn_chain"):
     return meta
 
 
-def bn_chain(z, stages, residual=None):
+def _out_dtype(out_dtype, z, who):
+    if out_dtype not in (None, torch.float32, torch.float16):
+        raise RuntimeError(f"{who}: out_dtype is None (float32), torch.float32 or torch.float16")
+    if out_dtype == torch.float16 and z.dtype != torch.float16:
+        raise RuntimeError(f"{who}: out_dtype=torch.float16 needs a float16 z")
+    return torch.float32 if out_dtype is None else out_dtype
+
+
+def bn_chain(z, stages, residual=None, out_dtype=None):
     """Everything the reference's ``InvertedResidualBlock`` (``model.py:46-85``) runs between two of its 1x1 convolutions, on the
     pre-activation ``z`` [M, C] in rows: for every stage of ``stages``, in order, an optional depthwise ``Conv1d(C, C, 1, groups=C)``
     (``w[c] * x + b[c]``), a ``torch.nn.BatchNorm1d`` and an optional ReLU; then, with ``residual`` [M, C], ``relu(x + residual)``.
@@ -718,12 +806,21 @@ def bn_chain(z, stages, residual=None):
     floating-point atomics: the same bits on every run.  Computes in fp32 under autocast.  Under ``no_grad`` the forward runs, the
     statistics move and nothing is saved.
 
+    dtypes: the result is fp32 (``out_dtype=None``).  A float16 ``z`` with a gradient to track is read as it is, is itself the tensor
+    saved for the backward, and gets its gradient written in float16 by the kernel (module switch ``half_io``, default True; False
+    casts it to fp32 first and saves that copy - the same bits, more passes).  ``out_dtype=torch.float16``, legal with a float16 ``z``
+    and no residual only, stores the fp32 result rounded to nearest even, which is what a following autocast GEMM would make of it:
+    ask for it only where the result goes into ``F.linear`` and nowhere else - never where a ReLU mask is taken from it.
+
     Every ``bn`` must be in the same mode.  In eval mode this is the plain composition on the running statistics.  ``affine=False``,
     ``track_running_stats=False``, ``momentum=None`` and a depthwise convolution without a bias raise ``NotImplementedError``; fewer
     than two rows in training mode raise PyTorch's ``ValueError``."""
     _lib.require_cuda(z, residual)
     if z.dim() != 2:
         raise RuntimeError("bn_chain: z [M, C]")
+    out_dtype = _out_dtype(out_dtype, z, "bn_chain")
+    if out_dtype == torch.float16 and residual is not None:
+        raise RuntimeError("bn_chain: out_dtype=torch.float16 is for a chain without a residual (its output is the last ReLU's mask)")
     if not 1 <= len(stages) <= _lib.BN_CHAIN_MAX:
         raise RuntimeError(f"bn_chain: one to {_lib.BN_CHAIN_MAX} stages")
     meta = _chain_normalise(stages, z.shape[1])
@@ -739,7 +836,8 @@ def bn_chain(z, stages, residual=None):
             x = bn(x)
             if relu:
                 x = torch.relu(x)
-        return x if residual is None else torch.relu(x + residual)
+        x = x if residual is None else torch.relu(x + residual)
+        return x.to(out_dtype) if out_dtype == torch.float16 else x
     if z.shape[0] < 2:
         raise ValueError(f"Expected more than 1 value per channel when training, got input size {z.size()}")
     for bn, _, _ in meta:
@@ -750,8 +848,10 @@ def bn_chain(z, stages, residual=None):
         params += [bn.weight, bn.bias] + ([dw.weight, dw.bias] if dw is not None else [])
     flags = [(bn, relu, dw is not None) for bn, relu, dw in meta]
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (z, residual, *params)):
-        return _BnChain.apply(z, residual, flags, *params)
-    return _bn_chain_forward(_f32c(z), None if residual is None else _f32c(residual), flags, [_f32c(p.reshape(-1)) for p in params])[0]
+        if _keeps_half(z):
+            return _BnChainHalf.apply(z, residual, flags, out_dtype, *params)
+        return _BnChain.apply(z, residual, flags, *params).to(out_dtype)
+    return _bn_chain_forward(_f32c(z), None if residual is None else _f32c(residual), flags, [_f32c(p.reshape(-1)) for p in params])[0].to(out_dtype)
 
 
 class _DepthwiseSeparable(torch.nn.Module):
@@ -763,6 +863,12 @@ class _DepthwiseSeparable(torch.nn.Module):
         self.depthwise_bn = torch.nn.BatchNorm1d(channels)
         self.pointwise_conv = torch.nn.Conv1d(channels, channels, kernel_size=1)
         self.pointwise_bn = torch.nn.BatchNorm1d(channels)
+
+
+def _gemm_dtype(z):
+    """The ``out_dtype`` of a result that goes straight into ``F.linear`` and nowhere else: float16 where ``half_io`` is on and the
+    GEMM that made ``z`` ran in float16 under autocast - the next one would round an fp32 result the same way - else None (fp32)."""
+    return torch.float16 if half_io and z.dtype == torch.float16 and torch.is_autocast_enabled("cuda") else None
 
 
 def _rows_conv(conv, x):
@@ -797,9 +903,13 @@ class InvertedResidualBlock(torch.nn.Module):
         if not self.training:
             return self._forward_plain(x)
         d0, d3 = self.conv[0], self.conv[3]
-        h = bn_chain(_rows_conv(self.expand[0], x), [(self.expand[1], True), (d0.depthwise_bn, True, d0.depthwise_conv)])
-        h = bn_chain(_rows_conv(d0.pointwise_conv, h), [(d0.pointwise_bn, True), (self.conv[1], True), (d3.depthwise_bn, True, d3.depthwise_conv)])
-        h = bn_chain(_rows_conv(d3.pointwise_conv, h), [(d3.pointwise_bn, True), (self.conv[4], False)])
+        # (the first three results go into the next GEMM and nowhere else: float16 where the GEMMs run in float16, _gemm_dtype)
+        z = _rows_conv(self.expand[0], x)
+        h = bn_chain(z, [(self.expand[1], True), (d0.depthwise_bn, True, d0.depthwise_conv)], out_dtype=_gemm_dtype(z))
+        z = _rows_conv(d0.pointwise_conv, h)
+        h = bn_chain(z, [(d0.pointwise_bn, True), (self.conv[1], True), (d3.depthwise_bn, True, d3.depthwise_conv)], out_dtype=_gemm_dtype(z))
+        z = _rows_conv(d3.pointwise_conv, h)
+        h = bn_chain(z, [(d3.pointwise_bn, True), (self.conv[4], False)], out_dtype=_gemm_dtype(z))
         res = bn_chain(_rows_conv(self.shortcut[0], x), [(self.shortcut[1], False)]) if len(self.shortcut) else x
         return bn_chain(_rows_conv(self.project[0], h), [(self.project[1], False)], residual=res)
 
@@ -899,15 +1009,16 @@ def _relu_bn_ws(M, C, dev):
     return torch.empty(need, dtype=torch.uint8, device=dev)
 
 
-def _relu_bn_forward(zc, gamma, beta, bn):
-    """(out, mean, invstd) of ``p2w_relu_bn`` on fp32, contiguous inputs; bn's running statistics move in place."""
+def _relu_bn_forward(zc, gamma, beta, bn, out_dtype=torch.float32):
+    """(out, mean, invstd) of ``p2w_relu_bn_io`` on a contiguous fp32 or float16 z (the vectors fp32); bn's running statistics move in
+    place."""
     (M, C), dev = zc.shape, zc.device
-    out = torch.empty((M, C), dtype=torch.float32, device=dev)
+    out = torch.empty((M, C), dtype=out_dtype, device=dev)
     mean, invstd = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(2))
     rm, rv = (t.detach().to(torch.float32).contiguous() for t in (bn.running_mean, bn.running_var))
     ws = _relu_bn_ws(M, C, dev)
-    check(lib().p2w_relu_bn(ptr(zc), C, ptr(gamma), ptr(beta), ptr(rm), ptr(rv), float(bn.momentum), float(bn.eps), M, C, ptr(out), C,
-                            ptr(mean), ptr(invstd), ptr(ws), ws.numel(), stream()), "relu_bn")
+    check(lib().p2w_relu_bn_io(ptr(zc), _code(zc), C, ptr(gamma), ptr(beta), ptr(rm), ptr(rv), float(bn.momentum), float(bn.eps), M, C, ptr(out),
+                               _code(out), C, ptr(mean), ptr(invstd), ptr(ws), ws.numel(), stream()), "relu_bn")
     with torch.no_grad():
         for mine, theirs in ((rm, bn.running_mean), (rv, bn.running_var)):
             if mine.data_ptr() != theirs.data_ptr():
@@ -920,29 +1031,52 @@ class _ReluBn(torch.autograd.Function):
     invstd and gamma - no [M, C] tensor besides z itself."""
 
     @staticmethod
-    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, z, gamma, beta, bn):
-        zc, gc = _f32c(z), _f32c(gamma)
-        out, mean, invstd = _relu_bn_forward(zc, gc, _f32c(beta), bn)
+    def _forward(ctx, z, gamma, beta, bn, out_dtype=torch.float32, keeps_half=False):
+        zc, gc = z.detach().contiguous() if keeps_half else _f32c(z), _f32c(gamma)
+        out, mean, invstd = _relu_bn_forward(zc, gc, _f32c(beta), bn, out_dtype)
         ctx.save_for_backward(zc, mean, invstd, gc)
         ctx.dtypes = (z.dtype, gamma.dtype, beta.dtype)
         return out
 
     @staticmethod
-    @torch.amp.custom_bwd(device_type="cuda")
-    def backward(ctx, grad_out):
+    def _backward(ctx, grad_out):
         z, mean, invstd, gamma = ctx.saved_tensors
         (M, C), dev = z.shape, z.device
-        g = _f32c(grad_out)
-        dz = torch.empty((M, C), dtype=torch.float32, device=dev)
+        g = _grad_for(grad_out, z)
+        dz = torch.empty((M, C), dtype=z.dtype, device=dev)
         dgamma, dbeta = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(2))
         ws = _relu_bn_ws(M, C, dev)
-        check(lib().p2w_relu_bn_bwd(ptr(g), C, ptr(z), C, ptr(gamma), ptr(mean), ptr(invstd), M, C, ptr(dz), C, ptr(dgamma), ptr(dbeta),
-                                    ptr(ws), ws.numel(), stream()), "relu_bn backward")
+        check(lib().p2w_relu_bn_bwd_io(ptr(g), _code(g), C, ptr(z), _code(z), C, ptr(gamma), ptr(mean), ptr(invstd), M, C, ptr(dz), C, ptr(dgamma),
+                                       ptr(dbeta), ptr(ws), ws.numel(), stream()), "relu_bn backward")
         return dz.to(ctx.dtypes[0]), dgamma.to(ctx.dtypes[1]), dbeta.to(ctx.dtypes[2]), None
 
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, z, gamma, beta, bn):
+        return _ReluBn._forward(ctx, z, gamma, beta, bn)
 
-def relu_bn(z, bn):
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_out):
+        return _ReluBn._backward(ctx, grad_out)
+
+
+class _ReluBnHalf(_ReluBn):
+    """``_ReluBn`` on a float16 ``z`` as it is (``half_io``): ``z`` itself is saved, the output is fp32 or float16, its gradient is read
+    in the dtype it arrives in and ``dz`` is written in float16 by the kernel."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, bn, out_dtype):
+        with _no_autocast():
+            return _ReluBn._forward(ctx, z, gamma, beta, bn, out_dtype, keeps_half=True)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        with _no_autocast():
+            return (*_ReluBn._backward(ctx, grad_out), None)
+
+
+def relu_bn(z, bn, out_dtype=None):
     """``bn(torch.relu(z))`` for a ``torch.nn.BatchNorm1d`` ``bn`` in training mode on the pre-activation ``z`` [M, C] in rows: the tail
     of every later layer of the reference's ``MLP`` (``model.py:198-202``: Linear, ReLU, BatchNorm1d).  By definition the one-stage
     ``bn_chain`` on ``relu(z)`` - the same device code with the ReLU applied as ``z`` is loaded (``csrc/p2w_bnchain.hip``), so the output,
@@ -951,7 +1085,9 @@ def relu_bn(z, bn):
     gradient read twice, the gradient with respect to ``z`` written once (``dz = 0`` where ``z <= 0``); three launches each way.
     Gradients go to ``z``, ``bn.weight`` and ``bn.bias`` in their dtypes.  Running statistics (unbiased variance) and
     ``num_batches_tracked`` update as PyTorch's.  No floating-point atomics: the same bits on every run.  Computes in fp32 under
-    autocast.  Under ``no_grad`` the forward runs, the statistics move and nothing is saved.
+    autocast.  Under ``no_grad`` the forward runs, the statistics move and nothing is saved.  dtypes, ``half_io`` and ``out_dtype`` as
+    ``bn_chain``'s: a float16 ``z`` is read and saved as it is, ``out_dtype=torch.float16`` only where the result goes into ``F.linear``
+    alone.
 
     In eval mode this is ``bn(torch.relu(z))`` itself.  ``affine=False``, ``track_running_stats=False`` and ``momentum=None`` raise
     ``NotImplementedError``; fewer than two rows in training mode raise PyTorch's ``ValueError``."""
@@ -962,15 +1098,19 @@ def relu_bn(z, bn):
         raise NotImplementedError("relu_bn supports BatchNorm1d(affine=True, track_running_stats=True, momentum=<float>) as the reference builds it")
     if z.dim() != 2 or z.shape[1] != bn.num_features:
         raise RuntimeError("relu_bn: z [M, C] with C = bn.num_features")
+    out_dtype = _out_dtype(out_dtype, z, "relu_bn")
     if not bn.training:
-        return bn(torch.relu(z))
+        x = bn(torch.relu(z))
+        return x.to(out_dtype) if out_dtype == torch.float16 else x
     if z.shape[0] < 2:
         raise ValueError(f"Expected more than 1 value per channel when training, got input size {z.size()}")
     if bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
     if torch.is_grad_enabled() and (z.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad):
-        return _ReluBn.apply(z, bn.weight, bn.bias, bn)
-    return _relu_bn_forward(_f32c(z), _f32c(bn.weight), _f32c(bn.bias), bn)[0]
+        if _keeps_half(z):
+            return _ReluBnHalf.apply(z, bn.weight, bn.bias, bn, out_dtype)
+        return _ReluBn.apply(z, bn.weight, bn.bias, bn).to(out_dtype)
+    return _relu_bn_forward(_f32c(z), _f32c(bn.weight), _f32c(bn.bias), bn)[0].to(out_dtype)
 
 
 # --------------------------------------------------------------------------- the head behind conv1 for training
@@ -982,14 +1122,15 @@ def _head_ws(M, C, dev):
 
 
 def _bn_relu_rowdot_forward(zc, gamma, beta, w, b, bn):
-    """(logit, mean, invstd) of ``p2w_bn_relu_rowdot`` on fp32, contiguous inputs; bn's running statistics move in place."""
+    """(logit, mean, invstd) of ``p2w_bn_relu_rowdot_io`` on a contiguous fp32 or float16 z (the vectors fp32); bn's running statistics
+    move in place."""
     (M, C), dev = zc.shape, zc.device
     logit = torch.empty(M, dtype=torch.float32, device=dev)
     mean, invstd = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(2))
     rm, rv = (t.detach().to(torch.float32).contiguous() for t in (bn.running_mean, bn.running_var))
     ws = _head_ws(M, C, dev)
-    check(lib().p2w_bn_relu_rowdot(ptr(zc), C, ptr(gamma), ptr(beta), ptr(w), ptr(b), ptr(rm), ptr(rv), float(bn.momentum), float(bn.eps),
-                                   M, C, ptr(logit), ptr(mean), ptr(invstd), ptr(ws), ws.numel(), stream()), "bn_relu_rowdot")
+    check(lib().p2w_bn_relu_rowdot_io(ptr(zc), _code(zc), C, ptr(gamma), ptr(beta), ptr(w), ptr(b), ptr(rm), ptr(rv), float(bn.momentum),
+                                      float(bn.eps), M, C, ptr(logit), ptr(mean), ptr(invstd), ptr(ws), ws.numel(), stream()), "bn_relu_rowdot")
     with torch.no_grad():
         for mine, theirs in ((rm, bn.running_mean), (rv, bn.running_var)):
             if mine.data_ptr() != theirs.data_ptr():
@@ -1004,26 +1145,50 @@ class _BnReluRowdot(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, z, gamma, beta, weight, bias, bn):
-        zc, gc, bc, wc = _f32c(z), _f32c(gamma), _f32c(beta), _lib.aligned16(_f32c(weight.reshape(-1)))
+        return _BnReluRowdot._forward(ctx, z, gamma, beta, weight, bias, bn)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_out):
+        return _BnReluRowdot._backward(ctx, grad_out)
+
+    @staticmethod
+    def _forward(ctx, z, gamma, beta, weight, bias, bn, keeps_half=False):
+        zc = z.detach().contiguous() if keeps_half else _f32c(z)
+        gc, bc, wc = _f32c(gamma), _f32c(beta), _lib.aligned16(_f32c(weight.reshape(-1)))
         logit, mean, invstd = _bn_relu_rowdot_forward(zc, gc, bc, wc, _f32c(bias.reshape(-1)), bn)
         ctx.save_for_backward(zc, mean, invstd, gc, bc, wc)
         ctx.like = [(t.dtype, t.shape) for t in (z, gamma, beta, weight, bias)]
         return logit
 
     @staticmethod
-    @torch.amp.custom_bwd(device_type="cuda")
-    def backward(ctx, grad_out):
+    def _backward(ctx, grad_out):
         z, mean, invstd, gamma, beta, w = ctx.saved_tensors
         (M, C), dev = z.shape, z.device
         g = _f32c(grad_out)
-        dz = torch.empty((M, C), dtype=torch.float32, device=dev)
+        dz = torch.empty((M, C), dtype=z.dtype, device=dev)
         dgamma, dbeta, dw = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(3))
         dbias = torch.empty(1, dtype=torch.float32, device=dev)
         ws = _head_ws(M, C, dev)
-        check(lib().p2w_bn_relu_rowdot_bwd(ptr(g), ptr(z), C, ptr(gamma), ptr(beta), ptr(w), ptr(mean), ptr(invstd), M, C, ptr(dz), C,
-                                           ptr(dgamma), ptr(dbeta), ptr(dw), ptr(dbias), ptr(ws), ws.numel(), stream()),
+        check(lib().p2w_bn_relu_rowdot_bwd_io(ptr(g), ptr(z), _code(z), C, ptr(gamma), ptr(beta), ptr(w), ptr(mean), ptr(invstd), M, C, ptr(dz), C,
+                                              ptr(dgamma), ptr(dbeta), ptr(dw), ptr(dbias), ptr(ws), ws.numel(), stream()),
               "bn_relu_rowdot backward")
         return (*[gr.to(dt).reshape(shape) for gr, (dt, shape) in zip((dz, dgamma, dbeta, dw, dbias), ctx.like)], None)
+
+
+class _BnReluRowdotHalf(_BnReluRowdot):
+    """``_BnReluRowdot`` on a float16 ``z`` as it is (``half_io``): ``z`` itself is saved and ``dz`` is written in float16 by the kernel;
+    the logits and their gradient stay fp32."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, weight, bias, bn):
+        with _no_autocast():
+            return _BnReluRowdot._forward(ctx, z, gamma, beta, weight, bias, bn, keeps_half=True)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        with _no_autocast():
+            return _BnReluRowdot._backward(ctx, grad_out)
 
 
 def bn_relu_rowdot(z, bn, weight, bias):
@@ -1038,7 +1203,8 @@ def bn_relu_rowdot(z, bn, weight, bias):
     vectors.  Gradients go to ``z``, ``bn.weight``, ``bn.bias``, ``weight`` and ``bias`` in their dtypes and shapes.  A row's sum runs
     in an order fixed by C alone (``include/p2w.h``); no floating-point atomics: the same bits on every run.  Running statistics
     (unbiased variance) and ``num_batches_tracked`` update as PyTorch's.  Computes in fp32 under autocast.  Under ``no_grad`` the
-    forward runs, the statistics move and nothing is saved.
+    forward runs, the statistics move and nothing is saved.  A float16 ``z`` with a gradient to track is read and saved as it is and
+    gets a float16 gradient from the kernel (``half_io``); the logits are fp32 either way.
 
     In eval mode this is the plain composition on the running statistics.  ``affine=False``, ``track_running_stats=False`` and
     ``momentum=None`` raise ``NotImplementedError``; fewer than two rows in training mode raise PyTorch's ``ValueError``."""
@@ -1060,7 +1226,7 @@ def bn_relu_rowdot(z, bn, weight, bias):
     if bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
     if torch.is_grad_enabled() and any(t.requires_grad for t in (z, bn.weight, bn.bias, weight, bias)):
-        return _BnReluRowdot.apply(z, bn.weight, bn.bias, weight, bias, bn)
+        return (_BnReluRowdotHalf if _keeps_half(z) else _BnReluRowdot).apply(z, bn.weight, bn.bias, weight, bias, bn)
     return _bn_relu_rowdot_forward(_f32c(z), _f32c(bn.weight), _f32c(bn.bias), _lib.aligned16(_f32c(weight.reshape(-1))),
                                    _f32c(bias.reshape(-1)), bn)[0]
 
@@ -1101,6 +1267,8 @@ class FPModule(torch.nn.Module):
         Pc = torch.nn.functional.linear(x, lin0.weight[:, :Fc])                     # layer 0 on the coarse rows, no bias
         S = torch.nn.functional.linear(x_skip, lin0.weight[:, Fc:], lin0.bias)      # ... and on the fine rows
         h = interp_add_relu(Pc, S, pos, pos_skip, batch, batch_skip, k=self.k)
-        for layer in list(self.NN)[1:]:
-            h = relu_bn(layer[0](h), layer[2])
+        layers = list(self.NN)[1:]
+        for i, layer in enumerate(layers):      # (an inner result goes into the next GEMM alone: float16 where that GEMM's is; the last is returned)
+            z = layer[0](h)
+            h = relu_bn(z, layer[2], out_dtype=_gemm_dtype(z) if i + 1 < len(layers) else None)
         return h, pos_skip, batch_skip

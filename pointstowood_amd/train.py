@@ -177,7 +177,7 @@ class GlobalSAModule(torch.nn.Module):
             # here a target is a whole voxel of thousands of rows - with B targets a single item would walk the whole tensor
             lin0, lin1, bn = self.NN[0][0], self.NN[1][0], self.NN[1][2]
             h = torch.relu(F.linear(h, lin0.weight, lin0.bias))
-            h = ops.relu_bn(F.linear(h, lin1.weight, lin1.bias), bn)
+            h = ops.relu_bn(F.linear(h, lin1.weight, lin1.bias), bn)        # (fp32 out: it feeds a max, not a GEMM - ops.half_io)
         else:
             h = self.NN(h)
         pooled = ops.global_max_pool(h, batch)
