@@ -400,6 +400,34 @@ int32_t p2w_train_feed(const float* xyzr, const float* y, const int64_t* set_ptr
                        const float* noise, float* pos_out, float* refl_out, float* y_out, int64_t* batch_out, float* sf_out,
                        int32_t* nonfinite_out, uint32_t* words_out, void* ws, size_t ws_size, p2w_stream_t stream);
 
+/* The training sample: a uniformly random k-subset of {0 .. n-1}, ascending - the law of SAModule's draw (pointstowood/src/model.py:97-101:
+ * the first half of a randperm, sorted) as a function of (seed, c1, c2, n, k) alone, from the feed's generator and not from the reference's
+ * random stream.
+ *   key_i  = word w0 of Philox4x32-10 with counter (i, c1, c2, P2W_SAMPLE_STREAM) and key (seed & 0xffffffff, seed >> 32);
+ *   subset = the k rows that are smallest in the lexicographic order of (key_i, i);
+ *   idx_out[0..k) = those rows in ascending row order.
+ * As far as the words are independent and uniform, distinct keys make every k-subset equally likely.  Equal keys are ordered by row: with
+ * T the k-th smallest key, of the rows whose key is T the lowest ones are taken.  A given row shares the boundary value with another one
+ * with probability of order n 2^-32 (0.4 % at n = 2^24, 3e-5 at 131 072), and only then is the lower row preferred: the inclusion
+ * probabilities differ from k / n by that order at most.
+ * In : keys[n] uint32 (optional: NULL) = the key of every row, used IN PLACE of the generator.  Out: idx_out[k] int64; keys_out[n] uint32
+ *      (optional: NULL) = the key of every row.  All DEVICE memory.
+ * 0 <= k <= n <= P2W_SAMPLE_N_MAX = 2^24 (P2W_EINVAL; p2w_random_subset_ws_size returns 0 for an n outside).  n = 0 or k = 0: P2W_OK,
+ * nothing launched, nothing written.  k = n gives 0 .. n-1.  idx_out and ws required (P2W_ENULL); ws 16-byte, idx_out 8-byte, keys and
+ * keys_out 4-byte aligned (P2W_EALIGN); ws: p2w_random_subset_ws_size(n) bytes (4 bytes per row, four 256-bin histograms, two counters
+ * per tile of P2W_SAMPLE_TILE rows and their scan's tile sums; too small: P2W_EWORKSPACE).  A refused call launches nothing.
+ * An exact selection, not a sort: a radix select of T over four 8-bit digits, the most significant first, then a stable compaction.
+ * 8 launches for n <= 2^21, 10 above (zero the histograms, keys, three select passes, count, a scan of one or three launches, write).  No
+ * memset, no host synchronisation, no host read; no workgroup waits for another - what one launch needs of all workgroups of an earlier
+ * one is a launch boundary.  Integer arithmetic only; the atomics are integer additions to histogram bins (order-independent), so the
+ * bits are the same on every run and do not depend on what the workspace held. */
+#define P2W_SAMPLE_STREAM 0x50325753u /* "P2WS" */
+#define P2W_SAMPLE_TILE 1024
+#define P2W_SAMPLE_N_MAX ((int64_t)1 << 24)
+size_t p2w_random_subset_ws_size(int64_t n);
+int32_t p2w_random_subset(int64_t n, int64_t k, uint64_t seed, uint32_t c1, uint32_t c2, const uint32_t* keys, int64_t* idx_out,
+                          uint32_t* keys_out, void* ws, size_t ws_bytes, p2w_stream_t stream);
+
 /* PointCloudClassifier.compute_labels (predicter.py:112-127) over a neighbour table nbr[n,k] (indices into pred /
  * prob, deg[i] valid entries): pwood_out = median of the neighbours' probabilities (np.median: mean of the two middle
  * values for an even count); label_out: any_wood != 1 -> 1 if any neighbour's prediction > any_wood else 0;

@@ -42,6 +42,7 @@ EDGE_CHUNK = 1024                                                               
 BN_GROUP = 16                                                                                      # P2W_BN_GROUP
 BN_CHAIN_MAX, BN_CHAIN_ROWS = 3, 32                                                                # P2W_BN_CHAIN_*
 FEED_CHUNK, FEED_STREAM = 256, 0x50325746                                                          # P2W_FEED_*
+SAMPLE_STREAM, SAMPLE_TILE, SAMPLE_N_MAX = 0x50325753, 1024, 1 << 24                               # P2W_SAMPLE_*
 F32, F16 = 0, 1                                                                                    # P2W_F32, P2W_F16
 
 SIGNATURES = {
@@ -95,6 +96,8 @@ SIGNATURES = {
     "p2w_train_feed_ws_size": (_sz, [C.c_int64, _i32]),
     "p2w_train_feed": (_i32, [_vp, _vp, _vp, C.c_int64, _i32, _vp, _vp, _i32, C.c_int64, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp,
                               _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "p2w_random_subset_ws_size": (_sz, [C.c_int64]),
+    "p2w_random_subset": (_i32, [C.c_int64, C.c_int64, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "p2w_tile_bbox": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "p2w_tile_bbox_count": (_i32, [_i32, _i32]),
     "p2w_stem": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp]),

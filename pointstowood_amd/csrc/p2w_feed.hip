@@ -19,6 +19,7 @@
 // Every index that reaches memory is clamped: offsets into [0, n] and [0, n_set], a voxel id outside [0, V) is an empty voxel, and a
 // voxel is as long as the shorter of its out_ptr and set_ptr ranges.
 #include "p2w_common.h"
+#include "p2w_philox.h"
 #include <math.h>
 
 namespace {
@@ -109,19 +110,6 @@ __global__ __launch_bounds__(FD_THREADS) void fd_sum_kernel(const float4* __rest
     }
 }
 
-// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11): ten rounds, the key bumped by the
-// Weyl constants between rounds
-__device__ __forceinline__ void fd_philox(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned w[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
-}
-
 // the standard normal of include/p2w.h, bit by bit: u1 in (0, 1] and u2 in [0, 1) from the top 24 bits of words 0 and 1
 __device__ __forceinline__ float fd_normal(const unsigned w[4]) {
     const float u1 = (float)((w[0] >> 8) + 1u) * 0x1p-24f;
@@ -169,7 +157,7 @@ __global__ __launch_bounds__(FD_THREADS) void fd_write_kernel(const float4* __re
         const bool draw = rec.refl_mode == 2 && noise == nullptr;
         if (draw || words_out != nullptr) {
             unsigned w[4];
-            fd_philox((unsigned)(k.j * P2W_FEED_CHUNK + threadIdx.x), (unsigned)k.id, epoch, P2W_FEED_STREAM, k0, k1, w);
+            p2w_philox((unsigned)(k.j * P2W_FEED_CHUNK + threadIdx.x), (unsigned)k.id, epoch, P2W_FEED_STREAM, k0, k1, w);
             if (words_out != nullptr) { words_out[4 * o] = w[0]; words_out[4 * o + 1] = w[1]; words_out[4 * o + 2] = w[2]; words_out[4 * o + 3] = w[3]; }
             if (draw) refl = v.w + 0.1f * fd_normal(w);
         }

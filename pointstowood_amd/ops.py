@@ -1272,3 +1272,36 @@ class FPModule(torch.nn.Module):
             z = layer[0](h)
             h = relu_bn(z, layer[2], out_dtype=_gemm_dtype(z) if i + 1 < len(layers) else None)
         return h, pos_skip, batch_skip
+
+
+def random_subset(n, k, seed, counter=(0, 0), device="cuda", keys=None, return_keys=False):
+    """A uniformly random ``k``-subset of ``range(n)`` as an ascending int64 ``[k]`` device tensor (``p2w_random_subset``,
+    ``csrc/p2w_sample.hip``): the ``k`` rows with the smallest ``(key, row)``, ``key`` = word 0 of Philox4x32-10 at counter
+    ``(row, counter[0], counter[1], P2W_SAMPLE_STREAM)`` under ``seed`` - a function of ``(seed, counter, n, k)`` alone, the same bits on
+    every run.  ``n``, ``k``, ``seed`` and the counter words are Python integers; the call is enqueued on the current stream and waits
+    for nothing.  ``keys`` (an int32 ``[n]`` device tensor holding the 32-bit patterns) replaces the generator; ``return_keys`` also
+    returns the key of every row, stored as int32."""
+    n, k, seed, c1, c2 = int(n), int(k), int(seed), int(counter[0]), int(counter[1])
+    if not 0 <= k <= n <= _lib.SAMPLE_N_MAX:
+        raise ValueError(f"random_subset: need 0 <= k <= n <= {_lib.SAMPLE_N_MAX}, got n = {n}, k = {k}")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("random_subset needs an MI355X (cuda) device; there is no CPU fallback")
+    if keys is not None:
+        _lib.require_cuda(keys)
+        if keys.dtype != torch.int32 or keys.shape != (n,):
+            raise ValueError("random_subset: keys must be an int32 tensor of n elements")
+        keys, device = keys.contiguous(), keys.device
+    with torch.cuda.device(device):
+        idx = torch.empty(k, dtype=torch.int64, device=device)
+        keys_out = torch.empty(n, dtype=torch.int32, device=device) if return_keys else None
+        if n > 0 and k > 0:
+            need = int(lib().p2w_random_subset_ws_size(n))
+            if need == 0:
+                raise RuntimeError(f"p2w_random_subset_ws_size({n}) failed")
+            ws = torch.empty(need, dtype=torch.uint8, device=device)
+            check(lib().p2w_random_subset(n, k, seed & 0xffffffffffffffff, c1 & 0xffffffff, c2 & 0xffffffff, ptr(keys), ptr(idx),
+                                          ptr(keys_out), ptr(ws), ws.numel(), stream()), "p2w_random_subset")
+        elif return_keys and n > 0:                              # k = 0 launches nothing: the keys come from a draw of one row
+            keys_out = random_subset(n, 1, seed, (c1, c2), device, keys, True)[1]
+    return (idx, keys_out) if return_keys else idx

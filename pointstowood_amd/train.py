@@ -12,7 +12,11 @@ operator route's modules - ``ops.PointNetConv``, ``ops.InvertedResidualBlock``, 
 other roundings, the same bits on every run); False runs the reference's statements one by one on ``torch.nn`` modules and the
 plain ``ops`` callables - the baseline of an A/B comparison.  Assigning ``net.fused`` on a ``Net`` instance assigns it on every
 submodule that has the switch (``ops.FPModule`` included).  ``ops.PointNetConv.fused_bn_max`` is a separate switch and is not
-touched.  Gradients with respect to positions are not provided."""
+touched.  Gradients with respect to positions are not provided.
+
+``sampler`` (attribute of ``Net`` and ``SAModule``, default None): a ``DeviceSampler`` draws the three training samples on the GPU
+(``ops.random_subset``) as a function of (seed, epoch, step, level) in place of the reference's CPU ``randperm`` - the same law, a
+uniform half of the level's rows, from another random stream.  None is the reference's draw."""
 from __future__ import annotations
 
 import torch
@@ -103,6 +107,22 @@ def _conv_plain(conv, x, pos_src, pos_dst, edge_index):
     return out if conv.global_nn is None else conv.global_nn(out)
 
 
+class DeviceSampler:
+    """The training sample of the three set-abstraction levels drawn on the device: level ``level`` of step ``step`` of epoch ``epoch``
+    keeps ``ops.random_subset(n, n // 2, seed, counter=(4 * step + level, epoch))`` - nothing of it depends on the process-wide
+    generators, so a run resumed at (epoch, step) draws what the uninterrupted run drew.  ``Net.forward`` advances ``step`` once per
+    training-mode forward; ``set_epoch`` starts an epoch at step 0; ``step`` may be assigned."""
+
+    def __init__(self, seed):
+        self.seed, self.epoch, self.step = int(seed), 0, 0
+
+    def set_epoch(self, epoch):
+        self.epoch, self.step = int(epoch), 0
+
+    def draw(self, level, n, device):
+        return ops.random_subset(n, n // 2, self.seed, counter=(4 * self.step + level, self.epoch), device=device)
+
+
 class SAModule(torch.nn.Module):
     """The reference's set-abstraction level (``model.py:87-127``): sample centres, search their neighbours, ``PointNetConv`` on
     positions divided by the voxel's ``sf``, the inverted residual block.
@@ -112,9 +132,14 @@ class SAModule(torch.nn.Module):
     is multiplied - but its six parameters still receive ZERO gradients, as they do in the reference.  One deviation: the reference
     skips the call (and leaves those gradients None) in a batch whose reflectance sums to exactly 0; here the zeros are attached
     regardless, which needs no host synchronisation.  ``fused = False``: the reference's statements, with the plain compositions of
-    the conv and the block in both modes.  The caller's tensors are not written to."""
+    the conv and the block in both modes.  The caller's tensors are not written to.
+
+    ``sampler`` (default None): in training mode a ``DeviceSampler`` draws the sample as this module's ``level`` (0, 1, 2 in ``Net``) and
+    ``random_sample`` is not called; eval mode never looks at it."""
 
     fused = True
+    sampler = None
+    level = 0
 
     def __init__(self, resolution, radius, k, NN, RNN):
         super().__init__()
@@ -137,7 +162,10 @@ class SAModule(torch.nn.Module):
         if not self.fused and torch.sum(reflectance) != 0:
             gated = reflectance * self.reflectanceyesno(reflectance.unsqueeze(-1), batch)
         if self.training:
-            keep = self.random_sample(xyz.shape[0]).to(xyz.device)          # the one host-to-device copy of the index
+            if self.sampler is not None:
+                keep = self.sampler.draw(self.level, xyz.shape[0], xyz.device)
+            else:
+                keep = self.random_sample(xyz.shape[0]).to(xyz.device)      # the one host-to-device copy of the index
         else:
             keep = self.voxelsample(xyz, batch, self.resolution)
         centres, centre_batch = xyz[keep], batch[keep]
@@ -190,9 +218,11 @@ class Net(torch.nn.Module):
     feature-propagation levels and the head, on rows.  Training with ``fused = True`` and ``num_classes == 1`` (what the trainer
     builds) runs the head behind ``conv1`` as ``ops.bn_relu_rowdot``: neither ``relu(norm(conv1(x)))`` [N, 16 C] nor its gradient is
     formed.  More classes, eval mode and ``fused = False`` run the plain statements.  The output is [N] float32 for one class
-    ([num_classes, N] otherwise), as the reference's."""
+    ([num_classes, N] otherwise), as the reference's.  Assigning ``net.sampler`` hands the object to the three set-abstraction
+    levels; a training-mode forward with a sampler ends with ``sampler.step += 1``."""
 
     fused = True
+    sampler = None
 
     def __init__(self, num_classes, C=32):
         super().__init__()
@@ -200,6 +230,7 @@ class Net(torch.nn.Module):
         self.stem_mlp = MLP([3, C])
         for level, (resolution, (channels, width)) in enumerate(zip((0.04, 0.08, 0.16), sa_channels(C)), start=1):
             setattr(self, f"sa{level}_module", SAModule(resolution, resolution, 32, channels, width))
+            getattr(self, f"sa{level}_module").level = level - 1
         self.sa4_module = GlobalSAModule([16 * C + 3, 16 * C, 16 * C])
         for level in (4, 3, 2, 1):
             setattr(self, f"fp{level}_module", ops.FPModule(2, fp_channels(C)[level]))
@@ -214,6 +245,10 @@ class Net(torch.nn.Module):
             for m in self.modules():
                 if m is not self and hasattr(type(m), "fused"):
                     m.fused = value
+        if name == "sampler":
+            for m in self.modules():
+                if isinstance(m, SAModule):
+                    m.sampler = value
 
     def forward(self, data):
         data.x = self.stem_mlp(data.pos[:, :3])                  # the reference leaves the stem features on the batch
@@ -226,6 +261,8 @@ class Net(torch.nn.Module):
         for fp, skip in zip((self.fp4_module, self.fp3_module, self.fp2_module, self.fp1_module), reversed(skips)):
             coarse = fp(*coarse, *skip)
         z = F.linear(coarse[0], self.conv1.weight[:, :, 0], self.conv1.bias)
+        if self.training and self.sampler is not None:
+            self.sampler.step += 1                               # the next forward draws other samples
         if self.training and self.fused and self.num_classes == 1:
             return ops.bn_relu_rowdot(z, self.norm, self.conv2.weight, self.conv2.bias)
         out = F.linear(F.relu(self.norm(z)), self.conv2.weight[:, :, 0], self.conv2.bias)

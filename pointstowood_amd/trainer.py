@@ -84,8 +84,9 @@ def _save_best(model, stat, best, path):
 
 def SemanticTraining(args):
     """``args``: the namespace of ``train.py`` - ``wdir``, ``model``, ``trfile`` / ``tefile`` (voxel directories), ``batch_size``,
-    ``num_epochs``, ``checkpoints``, ``augmentation``, ``test``, ``tune``, ``stop_early``, ``wandb``, ``seed``; ``args.C`` (not on the
-    command line) is the network's width, 32 when absent.  Returns the history array."""
+    ``num_epochs``, ``checkpoints``, ``augmentation``, ``test``, ``tune``, ``stop_early``, ``wandb``, ``seed``, ``device_sample`` (absent
+    or False: the reference's CPU draw of the training sample); ``args.C`` (not on the command line) is the network's width, 32 when
+    absent.  Returns the history array."""
     if not torch.cuda.is_available():
         raise RuntimeError("SemanticTraining needs an MI355X (cuda) device; there is no CPU fallback")
     device = torch.device("cuda")
@@ -102,6 +103,8 @@ def SemanticTraining(args):
 
     model = _train.Net(num_classes=1, C=int(getattr(args, "C", 32))).to(device)
     print("Model contains", sum(p.numel() for p in model.parameters()), " parameters")
+    if getattr(args, "device_sample", False):                   # the training samples drawn on the GPU (train.DeviceSampler)
+        model.sampler = _train.DeviceSampler(seed)
 
     train_feed = TrainingFeed(TrainingSet(args.trfile, device), args.batch_size, shuffle=True, drop_last=True,
                               augmentation=args.augmentation, mode="train", seed=seed)
@@ -156,6 +159,8 @@ def SemanticTraining(args):
         print("\n=============================================================================================")
         print("EPOCH ", epoch)
         train_feed.set_epoch(epoch)
+        if model.sampler is not None:
+            model.sampler.set_epoch(epoch)
         scores = EpochScores(capacity=len(train_feed))
         for data in train_feed:
             optimizer.zero_grad()

@@ -32,6 +32,7 @@ static std::vector<Region> g_regions;
 #include "../pointstowood_amd/csrc/p2w_fp.hip"
 #include "../pointstowood_amd/csrc/p2w_head.hip"
 #include "../pointstowood_amd/csrc/p2w_feed.hip"
+#include "../pointstowood_amd/csrc/p2w_sample.hip"
 
 static int g_fail = 0, g_runs = 0;
 
@@ -75,6 +76,7 @@ int main() {
         check("ec_carve", n, 0, 0, [&](P2wArena& a) { ec_carve(a, n); });
         check("grow_carve", n, 0, 0, [&](P2wArena& a) { grow_carve(a, n); });
         check("lf_carve", n, 0, 0, [&](P2wArena& a) { lf_carve(a, n); });
+        check("sm_carve", n, 0, 0, [&](P2wArena& a) { sm_carve(a, n); });
         for (int flags : {0, (int)P2W_SA_PACK8}) check("sa_conv_carve", n, flags, 0, [&](P2wArena& a) { sa_conv_carve(a, (long)n, flags); });
         for (long long t : {0ll, 1ll, 257ll, 4097ll, 1ll << 22}) {
             check("tk_carve", n, t, 0, [&](P2wArena& a) { tk_carve(a, i, t); });

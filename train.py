@@ -44,6 +44,9 @@ def build_parser():
     # extensions of this build
     p.add_argument('--wdir', type=str, default=os.getcwd(), help='working directory with data/, model/ and checkpoints/')
     p.add_argument('--seed', type=int, default=141190, help='seed of the initialisation, the sampling and the feed')
+    p.add_argument('--device_sample', action='store_true',
+                   help="Draw each level's training sample on the GPU: the reference's law (a uniform half of the rows) from another "
+                        "random stream, a function of (seed, epoch, step, level), so a seeded run samples other points than without it")
     return p
 
 
