@@ -896,25 +896,35 @@ int32_t p2w_bn_relu_rowdot_bwd(const float* g, const float* z, int32_t ldz, cons
                                const float* mean, const float* invstd, int32_t M, int32_t C, float* dz, int32_t lddz, float* dgamma,
                                float* dbeta, float* dw, float* dbias, void* ws, size_t ws_bytes, p2w_stream_t stream);
 
-/* ---- the training operators on float16 tensors (pointstowood_amd/ops.py: half_io) ---- */
-/* Under autocast the GEMMs between the training operators give and take float16.  Each entry point below is its namesake with `void*`
- * for the [rows, C] tensors and one dtype code per tensor group, so that a float16 tensor is read and written as it is instead of
- * through an fp32 copy.  ONLY the element type at the loads and stores differs: every kernel widens a float16 element as it loads it
- * (exact) and computes in fp32 / fp64 exactly as its namesake - the same operations, sums, orders, launches and workspace (the
- * *_ws_size functions are shared) - and a float16 store rounds the fp32 result once, to nearest even, with overflow to +-inf,
- * gradual underflow to subnormals and +-0 and a NaN kept a NaN: torch.Tensor.half().  So every fp32 result equals the fp32 entry
- * point's on the widened tensors bit for bit, and every float16 result is that entry point's fp32 result rounded once.
- *   tz  z and dz          (p2w_bn_chain*, p2w_relu_bn*, p2w_bn_relu_rowdot*)
- *   to  out and g         (p2w_bn_chain*, p2w_relu_bn*); P2W_F16 only with tz = P2W_F16
- *   tx  x and grad_x      (p2w_segment_max_*); out, grad_out and arg stay fp32 / int32 (a maximum of widened values is exact)
+/* ---- the training operators on float16 and bfloat16 tensors (pointstowood_amd/ops.py: half_io) ---- */
+/* Under autocast the GEMMs between the training operators give and take float16 or bfloat16.  Each entry point below is its namesake
+ * with `void*` for the [rows, C] tensors and one dtype code per tensor group, so that a 16-bit tensor is read and written as it is
+ * instead of through an fp32 copy.  ONLY the element type at the loads and stores differs: every kernel widens a 16-bit element as it
+ * loads it (exact: a bfloat16's 16 bits become the top half of the fp32 pattern) and computes in fp32 / fp64 exactly as its namesake -
+ * the same operations, sums, orders, launches and workspace (the *_ws_size functions are shared) - and a 16-bit store rounds the fp32
+ * result once, to nearest, ties to the even mantissa:
+ *   float16   overflow to +-inf, gradual underflow to subnormals and +-0, a NaN kept a NaN: torch.Tensor.half();
+ *   bfloat16  a carry out of the largest finite value gives +-inf (the patterns 0x7F7F8000 and up), fp32 subnormals round to bfloat16
+ *             subnormals and +-0 (nothing is flushed), the sign of zero is kept, a NaN stays a NaN - one whose payload lies only in
+ *             the low 16 bits included, which a truncation would turn into an infinity: torch.Tensor.bfloat16().
+ * So every fp32 result equals the fp32 entry point's on the widened tensors bit for bit, and every 16-bit result is that entry
+ * point's fp32 result rounded once.
+ *   tz  z and dz          (p2w_bn_chain*, p2w_relu_bn*): P2W_F32, P2W_F16 or P2W_BF16; (p2w_bn_relu_rowdot*): P2W_F32 or P2W_F16
+ *   to  out and g         (p2w_bn_chain*, p2w_relu_bn*): P2W_F32, or equal to tz where tz is a 16-bit type
+ *   tx  x and grad_x      (p2w_segment_max_*): P2W_F32 or P2W_F16; out, grad_out and arg stay fp32 / int32 (a maximum of widened
+ *                         values is exact)
+ * The four chain entry points take P2W_BF16.  p2w_bn_relu_rowdot_io / _bwd_io and p2w_segment_max_arg_io / _bwd_io have one code
+ * each and answer 2 with P2W_EUNSUPPORTED like any other unknown code (tests/test_gpu_half_io.py: test_refusals_launch_nothing
+ * asserts it of them); their bfloat16 instantiations are the four p2w_*_bf16 entry points below the _io ones.
  * The residual, dres, the saved out of a chain with a residual, the logits and their gradient, every [C] / [L, C] vector and the
  * workspace stay fp32 / fp64.  Pitches are in elements.  Access width: a lane keeps its 4 adjacent columns, an 8-byte access on a
- * float16 tensor - it needs an 8-byte aligned pointer and a pitch divisible by 4 where an fp32 tensor needs 16 bytes; otherwise one
- * column per lane, the same bits.  Any other code, or a combination not listed: P2W_EUNSUPPORTED, checked first.  Every other
- * status code is the namesake's; a refused call launches nothing.  With P2W_F32 everywhere these ARE the fp32 entry points (which
- * call them). */
+ * 16-bit tensor - it needs an 8-byte aligned pointer and a pitch divisible by 4 where an fp32 tensor needs 16 bytes; otherwise one
+ * column per lane, the same bits.  Any other code, a float16 / bfloat16 mix, or a combination not listed: P2W_EUNSUPPORTED, checked
+ * first.  Every other status code is the namesake's; a refused call launches nothing.  With P2W_F32 everywhere these ARE the fp32
+ * entry points (which call them). */
 #define P2W_F32 0
 #define P2W_F16 1
+#define P2W_BF16 2
 int32_t p2w_bn_chain_io(const void* z, int32_t tz, int32_t ldz, const float* res, int32_t ldr, const p2w_bn_stage* stages, int32_t L,
                         int32_t M, int32_t C, void* out, int32_t to, int32_t ldo, float* mean, float* invstd, void* ws, size_t ws_bytes,
                         p2w_stream_t stream);
@@ -938,6 +948,21 @@ int32_t p2w_segment_max_arg_io(const void* x, int32_t tx, int32_t ldx, int32_t F
                                int32_t* arg, p2w_stream_t stream);
 int32_t p2w_segment_max_bwd_io(const float* grad_out, int32_t ldg, const int32_t* arg, const int32_t* ptr, int32_t B, int32_t F,
                                void* grad_x, int32_t tx, int32_t ldx, int32_t n, p2w_stream_t stream);
+/* The head and the segment max on bfloat16 tensors: what their _io entry points would do for tz / tx = P2W_BF16 - the namesake's
+ * arguments without the dtype code, z and dz (x and grad_x) bfloat16, everything else as above: the same launches, sums, workspace and
+ * status codes, the widening load exact, every bfloat16 store one rounding to nearest even, 8-byte accesses where an 8-byte aligned
+ * pointer and a pitch divisible by 4 allow. */
+int32_t p2w_bn_relu_rowdot_bf16(const void* z, int32_t ldz, const float* gamma, const float* beta, const float* w, const float* bias,
+                                float* running_mean, float* running_var, double momentum, double eps, int32_t M, int32_t C,
+                                float* logit, float* mean, float* invstd, void* ws, size_t ws_bytes, p2w_stream_t stream);
+int32_t p2w_bn_relu_rowdot_bwd_bf16(const float* g, const void* z, int32_t ldz, const float* gamma, const float* beta, const float* w,
+                                    const float* mean, const float* invstd, int32_t M, int32_t C, void* dz, int32_t lddz,
+                                    float* dgamma, float* dbeta, float* dw, float* dbias, void* ws, size_t ws_bytes,
+                                    p2w_stream_t stream);
+int32_t p2w_segment_max_arg_bf16(const void* x, int32_t ldx, int32_t F, const int32_t* ptr, int32_t B, float* out, int32_t* arg,
+                                 p2w_stream_t stream);
+int32_t p2w_segment_max_bwd_bf16(const float* grad_out, int32_t ldg, const int32_t* arg, const int32_t* ptr, int32_t B, int32_t F,
+                                 void* grad_x, int32_t ldx, int32_t n, p2w_stream_t stream);
 
 #ifdef __cplusplus
 }

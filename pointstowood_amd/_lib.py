@@ -43,7 +43,7 @@ BN_GROUP = 16                                                                   
 BN_CHAIN_MAX, BN_CHAIN_ROWS = 3, 32                                                                # P2W_BN_CHAIN_*
 FEED_CHUNK, FEED_STREAM = 256, 0x50325746                                                          # P2W_FEED_*
 SAMPLE_STREAM, SAMPLE_TILE, SAMPLE_N_MAX = 0x50325753, 1024, 1 << 24                               # P2W_SAMPLE_*
-F32, F16 = 0, 1                                                                                    # P2W_F32, P2W_F16
+F32, F16, BF16 = 0, 1, 2                                                                           # P2W_F32, P2W_F16, P2W_BF16
 
 SIGNATURES = {
     "p2w_version": (_i32, []),
@@ -162,6 +162,11 @@ SIGNATURES = {
                                          _vp]),
     "p2w_segment_max_arg_io": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     "p2w_segment_max_bwd_io": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "p2w_bn_relu_rowdot_bf16": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _i32, _i32, _vp, _vp, _vp, _vp, _sz,
+                                       _vp]),
+    "p2w_bn_relu_rowdot_bwd_bf16": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "p2w_segment_max_arg_bf16": (_i32, [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "p2w_segment_max_bwd_bf16": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp]),
 }
 
 _lib = None

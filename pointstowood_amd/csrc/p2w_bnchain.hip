@@ -20,9 +20,10 @@
 // Element types (the p2w_*_io entry points): TZ for z and dz, TO for out and g - float, or gr_half (p2w_runsum.h) widened as it is
 // loaded and rounded to nearest even by gr_f2h as it is stored.  Built: (float, float) - what the fp32 entry points run, the code it
 // was -, (gr_half, gr_half) for a chain between two float16 GEMMs and (gr_half, float) for one whose result is not only a GEMM's
-// input.  The residual, dres, the saved out of a chain with a residual (a ReLU mask), the [C] vectors and the workspace stay fp32 /
-// fp64; arithmetic, sums and their order do not depend on the element types, so a float16 route has the fp32 route's bits on the
-// widened tensors, rounded once where it stores float16.  V = 4 is an 8-byte access on a float16 tensor.
+// input; (gr_bf16, gr_bf16) and (gr_bf16, float) are the same two for bfloat16 (gr_f2b).  The residual, dres, the saved out of a
+// chain with a residual (a ReLU mask), the [C] vectors and the workspace stay fp32 / fp64; arithmetic, sums and their order do not
+// depend on the element types, so a 16-bit route has the fp32 route's bits on the widened tensors, rounded once where it stores
+// float16 / bfloat16.  V = 4 is an 8-byte access on a 16-bit tensor.
 #include "p2w_bnchain.h"
 
 namespace {
@@ -283,7 +284,8 @@ int32_t bc_chain_backward_t(bool pre, const TO* g, int32_t ldg, const TZ* z, int
     return P2W_LAUNCH_STATUS();
 }
 
-// the dtype codes of the _io entry points: (z, out) = (f32, f32), (f16, f32), (f16, f16); everything else is refused first
+// the dtype codes of the _io entry points: (z, out) = (f32, f32), (f16, f32), (f16, f16), (bf16, f32), (bf16, bf16); everything else
+// (a float16 / bfloat16 mix among it) is refused first
 int32_t bc_chain_forward(bool pre, const void* z, int32_t tz, int32_t ldz, const float* res, int32_t ldr, const p2w_bn_stage* stages, int32_t L,
                          int32_t M, int32_t C, void* out, int32_t to, int32_t ldo, float* mean, float* invstd, void* ws, size_t ws_bytes,
                          p2w_stream_t stream) {
@@ -291,6 +293,8 @@ int32_t bc_chain_forward(bool pre, const void* z, int32_t tz, int32_t ldz, const
     if (tz == P2W_F32 && to == P2W_F32) return BC_FWD(float, float);
     if (tz == P2W_F16 && to == P2W_F32) return BC_FWD(gr_half, float);
     if (tz == P2W_F16 && to == P2W_F16) return BC_FWD(gr_half, gr_half);
+    if (tz == P2W_BF16 && to == P2W_F32) return BC_FWD(gr_bf16, float);
+    if (tz == P2W_BF16 && to == P2W_BF16) return BC_FWD(gr_bf16, gr_bf16);
 #undef BC_FWD
     return P2W_EUNSUPPORTED;
 }
@@ -304,6 +308,8 @@ int32_t bc_chain_backward(bool pre, const void* g, int32_t to, int32_t ldg, cons
     if (tz == P2W_F32 && to == P2W_F32) return BC_BWD_T(float, float);
     if (tz == P2W_F16 && to == P2W_F32) return BC_BWD_T(gr_half, float);
     if (tz == P2W_F16 && to == P2W_F16) return BC_BWD_T(gr_half, gr_half);
+    if (tz == P2W_BF16 && to == P2W_F32) return BC_BWD_T(gr_bf16, float);
+    if (tz == P2W_BF16 && to == P2W_BF16) return BC_BWD_T(gr_bf16, gr_bf16);
 #undef BC_BWD_T
     return P2W_EUNSUPPORTED;
 }

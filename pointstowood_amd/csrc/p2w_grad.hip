@@ -9,7 +9,8 @@
 // allow it (V = 4), and falls back to 4-byte accesses (V = 1, still coalesced) for odd widths.
 // The segment max also takes a float16 x and writes a float16 grad_x (p2w_segment_max_arg_io / _bwd_io; TX = gr_half, p2w_runsum.h):
 // values are widened as they are loaded - a maximum of widened values is exact, so out stays fp32 - and the gathered gradient is
-// rounded to nearest even as it is stored; V = 4 is then an 8-byte access.
+// rounded to nearest even as it is stored; V = 4 is then an 8-byte access.  The same on a bfloat16 x (TX = gr_bf16):
+// p2w_segment_max_arg_bf16 / _bwd_bf16.
 #include "p2w_runsum.h"
 #include "p2w_segmax.h"
 
@@ -216,6 +217,9 @@ inline int32_t segmax_values(const float* x, int32_t ldx, int32_t F, const int32
 inline int32_t segmax_values(const gr_half* x, int32_t ldx, int32_t F, const int32_t* ptr, int32_t B, float* out, p2w_stream_t stream) {
     return segment_max_launch(x, ldx, F, ptr, B, out, p2w_s(stream));      // p2w_segment_max's kernels on the float16 element type
 }
+inline int32_t segmax_values(const gr_bf16* x, int32_t ldx, int32_t F, const int32_t* ptr, int32_t B, float* out, p2w_stream_t stream) {
+    return segment_max_launch(x, ldx, F, ptr, B, out, p2w_s(stream));      // ... and on the bfloat16 one
+}
 
 template <class TX>
 int32_t segmax_arg_t(const TX* x, int32_t ldx, int32_t F, const int32_t* ptr, int32_t B, float* out, int32_t* arg, p2w_stream_t stream) {
@@ -280,6 +284,17 @@ extern "C" int32_t p2w_segment_max_bwd_io(const float* grad_out, int32_t ldg, co
 extern "C" int32_t p2w_segment_max_bwd(const float* grad_out, int32_t ldg, const int32_t* arg, const int32_t* ptr, int32_t B, int32_t F,
                                        float* grad_x, int32_t ldx, int32_t n, p2w_stream_t stream) {
     return p2w_segment_max_bwd_io(grad_out, ldg, arg, ptr, B, F, grad_x, P2W_F32, ldx, n, stream);
+}
+
+// the bfloat16 instantiations (include/p2w.h: the dtype code 2 stays unknown to the two _io entry points above)
+extern "C" int32_t p2w_segment_max_arg_bf16(const void* x, int32_t ldx, int32_t F, const int32_t* ptr, int32_t B, float* out, int32_t* arg,
+                                            p2w_stream_t stream) {
+    return segmax_arg_t(static_cast<const gr_bf16*>(x), ldx, F, ptr, B, out, arg, stream);
+}
+
+extern "C" int32_t p2w_segment_max_bwd_bf16(const float* grad_out, int32_t ldg, const int32_t* arg, const int32_t* ptr, int32_t B, int32_t F,
+                                            void* grad_x, int32_t ldx, int32_t n, p2w_stream_t stream) {
+    return segmax_bwd_t(grad_out, ldg, arg, ptr, B, F, static_cast<gr_bf16*>(grad_x), ldx, n, stream);
 }
 
 extern "C" size_t p2w_interp_bwd_ws_bytes(int32_t m, int32_t kw, int32_t n_coarse) {

@@ -17,7 +17,7 @@
 //     order, fp64 partials per item, the items in ascending order.  The gradient of u is fl(g[r] w[c]), formed in registers from the
 //     M floats of g.
 //   TZ = the element type of z and dz (p2w_bn_relu_rowdot_io / _bwd_io): float, or gr_half widened on load and rounded to nearest even
-//     on store (p2w_runsum.h: gr_ld, gr_f2h); the logits, their gradient and every sum are what they are for float.
+//     on store (p2w_runsum.h: gr_ld, gr_f2h), or gr_bf16 likewise (gr_f2b; p2w_bn_relu_rowdot_bf16 / _bwd_bf16); the logits, their gradient and every sum are what they are for float.
 #include "p2w_bnchain.h"
 
 namespace {
@@ -268,4 +268,21 @@ extern "C" int32_t p2w_bn_relu_rowdot_bwd(const float* g, const float* z, int32_
                                           p2w_stream_t stream) {
     return p2w_bn_relu_rowdot_bwd_io(g, z, P2W_F32, ldz, gamma, beta, w, mean, invstd, M, C, dz, lddz, dgamma, dbeta, dw, dbias, ws, ws_bytes,
                                      stream);
+}
+
+// ---- the bfloat16 instantiations (include/p2w.h: the dtype code 2 stays unknown to the two _io entry points above)
+extern "C" int32_t p2w_bn_relu_rowdot_bf16(const void* z, int32_t ldz, const float* gamma, const float* beta, const float* w,
+                                           const float* bias, float* running_mean, float* running_var, double momentum, double eps,
+                                           int32_t M, int32_t C, float* logit, float* mean, float* invstd, void* ws, size_t ws_bytes,
+                                           p2w_stream_t stream) {
+    return hd_rowdot_t(static_cast<const gr_bf16*>(z), ldz, gamma, beta, w, bias, running_mean, running_var, momentum, eps, M, C, logit, mean,
+                       invstd, ws, ws_bytes, stream);
+}
+
+extern "C" int32_t p2w_bn_relu_rowdot_bwd_bf16(const float* g, const void* z, int32_t ldz, const float* gamma, const float* beta,
+                                               const float* w, const float* mean, const float* invstd, int32_t M, int32_t C, void* dz,
+                                               int32_t lddz, float* dgamma, float* dbeta, float* dw, float* dbias, void* ws,
+                                               size_t ws_bytes, p2w_stream_t stream) {
+    return hd_rowdot_bwd_t(g, static_cast<const gr_bf16*>(z), ldz, gamma, beta, w, mean, invstd, M, C, static_cast<gr_bf16*>(dz), lddz, dgamma,
+                           dbeta, dw, dbias, ws, ws_bytes, stream);
 }

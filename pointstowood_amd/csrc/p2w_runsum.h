@@ -52,7 +52,29 @@ template <int V> __device__ __forceinline__ void gr_st(gr_half* p, const float (
         *reinterpret_cast<gr_half4*>(p) = t;
     } else *p = gr_f2h(v[0]);
 }
-// a V = 4 access of element type T needs 4 sizeof(T) bytes of alignment: 16 for fp32, 8 for fp16
+// bfloat16 rows (P2W_BF16): the same scheme.  The widening load is exact - the 16 bits are the top half of the fp32 pattern.  EVERY
+// bf16 store goes through gr_f2b: one conversion per element, round to nearest even, a carry out of the largest finite value to
+// +-inf, fp32 subnormals to bf16 subnormals and +-0 (nothing flushed), a NaN stays a NaN whatever its payload - what
+// torch.Tensor.bfloat16() gives.  med3 stands between the value and the conversion for gr_f2h's reason.
+typedef __bf16 gr_bf16;
+typedef __bf16 gr_bf164 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ gr_bf16 gr_f2b(float f) {
+    return static_cast<gr_bf16>(__builtin_amdgcn_fmed3f(f, f, f));
+}
+template <int V> __device__ __forceinline__ void gr_ld(const gr_bf16* p, float (&v)[V]) {
+    if constexpr (V == 4) {
+        const gr_bf164 t = *reinterpret_cast<const gr_bf164*>(p);
+        v[0] = (float)t.x; v[1] = (float)t.y; v[2] = (float)t.z; v[3] = (float)t.w;
+    } else v[0] = (float)*p;
+}
+template <int V> __device__ __forceinline__ void gr_st(gr_bf16* p, const float (&v)[V]) {
+    if constexpr (V == 4) {
+        gr_bf164 t;
+        t.x = gr_f2b(v[0]); t.y = gr_f2b(v[1]); t.z = gr_f2b(v[2]); t.w = gr_f2b(v[3]);
+        *reinterpret_cast<gr_bf164*>(p) = t;
+    } else *p = gr_f2b(v[0]);
+}
+// a V = 4 access of element type T needs 4 sizeof(T) bytes of alignment: 16 for fp32, 8 for fp16 and bf16
 template <class T> inline bool gr_alv(const T* p) { return (reinterpret_cast<uintptr_t>(p) & (4 * sizeof(T) - 1)) == 0; }
 
 constexpr int RUN_SPLIT_MIN = 512;    // mean run length from which the runs are split over blocks

@@ -29,9 +29,10 @@ BatchNorm1d, ReLU, up to three times, and the residual add - computed from the G
 (``model.py:142-153``) trains through ``interp_add_relu`` (``csrc/p2w_fp.hip``: layer 0 hoisted behind the interpolation, the add and the
 ReLU in the interpolation's pass) and ``relu_bn`` (``csrc/p2w_bnchain.hip``: ReLU and training-mode BatchNorm1d from the GEMM's output).
 
-dtypes under autocast: ``bn_chain``, ``relu_bn``, ``bn_relu_rowdot`` and ``scatter_max`` / ``global_max_pool`` take a float16 tensor as it is,
-save that tensor and write a float16 gradient from the kernel (``half_io``, default True; False casts to fp32 first - the same bits);
-``bn_chain`` and ``relu_bn`` return float16 on request (``out_dtype``), for a result that goes into ``F.linear`` and nowhere else.
+dtypes under autocast: ``bn_chain``, ``relu_bn``, ``bn_relu_rowdot`` and ``scatter_max`` / ``global_max_pool`` take a float16 or bfloat16
+tensor as it is, save that tensor and write a gradient of its dtype from the kernel (``half_io``, default True; False casts to fp32
+first - the same bits); ``bn_chain`` and ``relu_bn`` return that dtype on request (``out_dtype``), for a result that goes into ``F.linear``
+and nowhere else.
 """
 from __future__ import annotations
 
@@ -149,20 +150,26 @@ def _wants_grad(x):
 # float16 by the kernel.  False: the route as it was - the big tensor is cast to fp32 first, that copy is saved, and the fp32
 # gradient is rounded in one more pass - launch for launch.  The two give the same bits everywhere: only the element type at the
 # loads and stores differs, and a float16 store is the one rounding the cast would have made.
+# bfloat16 (autocast with dtype=torch.bfloat16) takes the same two routes with its own element type: a bfloat16 store is the one
+# round-to-nearest-even conversion of torch.Tensor.bfloat16().  (The chain entry points take the dtype code P2W_BF16; the head and the
+# segment max have entry points of their own for bfloat16, p2w_*_bf16 - include/p2w.h.)
 half_io = True
+
+_HALF_TYPES = (torch.float16, torch.bfloat16)
+_CODES = {torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
 
 
 def _keeps_half(x):
-    return half_io and x.dtype == torch.float16 and x.is_cuda
+    return half_io and x.dtype in _HALF_TYPES and x.is_cuda
 
 
 def _code(t):
-    return _lib.F16 if t.dtype == torch.float16 else _lib.F32
+    return _CODES.get(t.dtype, _lib.F32)
 
 
 def _grad_for(grad_out, z):
-    """The output's gradient as the kernel reads it: float16 as it arrives where z is float16, fp32 otherwise."""
-    if z.dtype == torch.float16 and grad_out.dtype == torch.float16:
+    """The output's gradient as the kernel reads it: float16 / bfloat16 as it arrives where z has that dtype, fp32 otherwise."""
+    if z.dtype in _HALF_TYPES and grad_out.dtype == z.dtype:
         return grad_out.contiguous()
     return _f32c(grad_out)
 
@@ -191,7 +198,11 @@ class _SegmentMax(torch.autograd.Function):
         n, F = xc.shape
         out = torch.empty((nb, F), dtype=torch.float32, device=x.device)
         arg = torch.empty((nb, F), dtype=torch.int32, device=x.device)
-        check(lib().p2w_segment_max_arg_io(ptr(xc), _code(xc), F, F, ptr(csr), nb, ptr(out), ptr(arg), stream()), "segment_max_arg")
+        if xc.dtype == torch.bfloat16:
+            st = lib().p2w_segment_max_arg_bf16(ptr(xc), F, F, ptr(csr), nb, ptr(out), ptr(arg), stream())
+        else:
+            st = lib().p2w_segment_max_arg_io(ptr(xc), _code(xc), F, F, ptr(csr), nb, ptr(out), ptr(arg), stream())
+        check(st, "segment_max_arg")
         ctx.save_for_backward(arg, csr)
         ctx.shape, ctx.dtype, ctx.kernel_dtype = (n, F), x.dtype, xc.dtype
         return out
@@ -202,8 +213,11 @@ class _SegmentMax(torch.autograd.Function):
         n, F = ctx.shape
         g = grad_out.to(torch.float32).contiguous()
         grad_x = torch.empty((n, F), dtype=ctx.kernel_dtype, device=g.device)
-        check(lib().p2w_segment_max_bwd_io(ptr(g), F, ptr(arg), ptr(csr), arg.shape[0], F, ptr(grad_x), _code(grad_x), F, n, stream()),
-              "segment_max_bwd")
+        if grad_x.dtype == torch.bfloat16:
+            st = lib().p2w_segment_max_bwd_bf16(ptr(g), F, ptr(arg), ptr(csr), arg.shape[0], F, ptr(grad_x), F, n, stream())
+        else:
+            st = lib().p2w_segment_max_bwd_io(ptr(g), F, ptr(arg), ptr(csr), arg.shape[0], F, ptr(grad_x), _code(grad_x), F, n, stream())
+        check(st, "segment_max_bwd")
         return grad_x.to(ctx.dtype), None, None
 
     @staticmethod
@@ -218,7 +232,7 @@ class _SegmentMax(torch.autograd.Function):
 
 
 class _SegmentMaxHalf(_SegmentMax):
-    """``_SegmentMax`` on a float16 ``x`` as it is (``half_io``): no fp32 copy of ``x``, ``grad_x`` written in float16 by the kernel."""
+    """``_SegmentMax`` on a float16 or bfloat16 ``x`` as it is (``half_io``): no fp32 copy of ``x``, ``grad_x`` written in its dtype by the kernel."""
 
     @staticmethod
     def forward(ctx, x, csr, nb):
@@ -674,7 +688,7 @@ def _chain_ws(M, C, L, dev):
 
 
 def _bn_chain_forward(zc, rc, meta, vec, out_dtype=torch.float32):
-    """(out, mean, invstd) of ``p2w_bn_chain_io`` on a contiguous fp32 or float16 z (everything else fp32, contiguous); every bn's
+    """(out, mean, invstd) of ``p2w_bn_chain_io`` on a contiguous fp32, float16 or bfloat16 z (everything else fp32, contiguous); every bn's
     running statistics move in place."""
     (M, C), L, dev = zc.shape, len(meta), zc.device
     out = torch.empty((M, C), dtype=out_dtype, device=dev)
@@ -744,8 +758,8 @@ class _BnChain(torch.autograd.Function):
 
 
 class _BnChainHalf(_BnChain):
-    """``_BnChain`` on a float16 ``z`` as it is (``half_io``): ``z`` itself is saved, the output is fp32 or float16, its gradient is read in
-    the dtype it arrives in and ``dz`` is written in float16 by the kernel.  Parameters, the residual and the saved output of a chain
+    """``_BnChain`` on a float16 or bfloat16 ``z`` as it is (``half_io``): ``z`` itself is saved, the output is fp32 or ``z``'s dtype, its
+    gradient is read in the dtype it arrives in and ``dz`` is written in ``z``'s dtype by the kernel.  Parameters, the residual and the saved output of a chain
     with a residual stay fp32."""
 
     @staticmethod
@@ -781,10 +795,11 @@ def _chain_normalise(stages, C, who="bn_chain"):
 
 
 def _out_dtype(out_dtype, z, who):
-    if out_dtype not in (None, torch.float32, torch.float16):
-        raise RuntimeError(f"{who}: out_dtype is None (float32), torch.float32 or torch.float16")
-    if out_dtype == torch.float16 and z.dtype != torch.float16:
-        raise RuntimeError(f"{who}: out_dtype=torch.float16 needs a float16 z")
+    if out_dtype not in (None, torch.float32, *_HALF_TYPES):
+        raise RuntimeError(f"{who}: out_dtype is None (float32), torch.float32, torch.float16 or torch.bfloat16")
+    if out_dtype in _HALF_TYPES and z.dtype != out_dtype:
+        name = str(out_dtype).split(".")[-1]
+        raise RuntimeError(f"{who}: out_dtype=torch.{name} needs a {name} z")
     return torch.float32 if out_dtype is None else out_dtype
 
 
@@ -810,7 +825,8 @@ def bn_chain(z, stages, residual=None, out_dtype=None):
     saved for the backward, and gets its gradient written in float16 by the kernel (module switch ``half_io``, default True; False
     casts it to fp32 first and saves that copy - the same bits, more passes).  ``out_dtype=torch.float16``, legal with a float16 ``z``
     and no residual only, stores the fp32 result rounded to nearest even, which is what a following autocast GEMM would make of it:
-    ask for it only where the result goes into ``F.linear`` and nowhere else - never where a ReLU mask is taken from it.
+    ask for it only where the result goes into ``F.linear`` and nowhere else - never where a ReLU mask is taken from it.  A bfloat16
+    ``z`` (autocast with ``dtype=torch.bfloat16``) is treated the same way, with ``out_dtype=torch.bfloat16``.
 
     Every ``bn`` must be in the same mode.  In eval mode this is the plain composition on the running statistics.  ``affine=False``,
     ``track_running_stats=False``, ``momentum=None`` and a depthwise convolution without a bias raise ``NotImplementedError``; fewer
@@ -819,8 +835,8 @@ def bn_chain(z, stages, residual=None, out_dtype=None):
     if z.dim() != 2:
         raise RuntimeError("bn_chain: z [M, C]")
     out_dtype = _out_dtype(out_dtype, z, "bn_chain")
-    if out_dtype == torch.float16 and residual is not None:
-        raise RuntimeError("bn_chain: out_dtype=torch.float16 is for a chain without a residual (its output is the last ReLU's mask)")
+    if out_dtype in _HALF_TYPES and residual is not None:
+        raise RuntimeError("bn_chain: out_dtype=torch.float16 / torch.bfloat16 is for a chain without a residual (its output is the last ReLU's mask)")
     if not 1 <= len(stages) <= _lib.BN_CHAIN_MAX:
         raise RuntimeError(f"bn_chain: one to {_lib.BN_CHAIN_MAX} stages")
     meta = _chain_normalise(stages, z.shape[1])
@@ -837,7 +853,7 @@ def bn_chain(z, stages, residual=None, out_dtype=None):
             if relu:
                 x = torch.relu(x)
         x = x if residual is None else torch.relu(x + residual)
-        return x.to(out_dtype) if out_dtype == torch.float16 else x
+        return x.to(out_dtype) if out_dtype in _HALF_TYPES else x
     if z.shape[0] < 2:
         raise ValueError(f"Expected more than 1 value per channel when training, got input size {z.size()}")
     for bn, _, _ in meta:
@@ -866,9 +882,12 @@ class _DepthwiseSeparable(torch.nn.Module):
 
 
 def _gemm_dtype(z):
-    """The ``out_dtype`` of a result that goes straight into ``F.linear`` and nowhere else: float16 where ``half_io`` is on and the
-    GEMM that made ``z`` ran in float16 under autocast - the next one would round an fp32 result the same way - else None (fp32)."""
-    return torch.float16 if half_io and z.dtype == torch.float16 and torch.is_autocast_enabled("cuda") else None
+    """The ``out_dtype`` of a result that goes straight into ``F.linear`` and nowhere else: ``z``'s float16 or bfloat16 where ``half_io``
+    is on and the GEMM that made ``z`` ran in that dtype under autocast - the next one would round an fp32 result the same way - else
+    None (fp32)."""
+    if half_io and z.dtype in _HALF_TYPES and torch.is_autocast_enabled("cuda") and z.dtype == torch.get_autocast_dtype("cuda"):
+        return z.dtype
+    return None
 
 
 def _rows_conv(conv, x):
@@ -1010,7 +1029,7 @@ def _relu_bn_ws(M, C, dev):
 
 
 def _relu_bn_forward(zc, gamma, beta, bn, out_dtype=torch.float32):
-    """(out, mean, invstd) of ``p2w_relu_bn_io`` on a contiguous fp32 or float16 z (the vectors fp32); bn's running statistics move in
+    """(out, mean, invstd) of ``p2w_relu_bn_io`` on a contiguous fp32, float16 or bfloat16 z (the vectors fp32); bn's running statistics move in
     place."""
     (M, C), dev = zc.shape, zc.device
     out = torch.empty((M, C), dtype=out_dtype, device=dev)
@@ -1062,8 +1081,8 @@ class _ReluBn(torch.autograd.Function):
 
 
 class _ReluBnHalf(_ReluBn):
-    """``_ReluBn`` on a float16 ``z`` as it is (``half_io``): ``z`` itself is saved, the output is fp32 or float16, its gradient is read
-    in the dtype it arrives in and ``dz`` is written in float16 by the kernel."""
+    """``_ReluBn`` on a float16 or bfloat16 ``z`` as it is (``half_io``): ``z`` itself is saved, the output is fp32 or ``z``'s dtype, its
+    gradient is read in the dtype it arrives in and ``dz`` is written in ``z``'s dtype by the kernel."""
 
     @staticmethod
     def forward(ctx, z, gamma, beta, bn, out_dtype):
@@ -1101,7 +1120,7 @@ def relu_bn(z, bn, out_dtype=None):
     out_dtype = _out_dtype(out_dtype, z, "relu_bn")
     if not bn.training:
         x = bn(torch.relu(z))
-        return x.to(out_dtype) if out_dtype == torch.float16 else x
+        return x.to(out_dtype) if out_dtype in _HALF_TYPES else x
     if z.shape[0] < 2:
         raise ValueError(f"Expected more than 1 value per channel when training, got input size {z.size()}")
     if bn.num_batches_tracked is not None:
@@ -1122,15 +1141,19 @@ def _head_ws(M, C, dev):
 
 
 def _bn_relu_rowdot_forward(zc, gamma, beta, w, b, bn):
-    """(logit, mean, invstd) of ``p2w_bn_relu_rowdot_io`` on a contiguous fp32 or float16 z (the vectors fp32); bn's running statistics
+    """(logit, mean, invstd) of ``p2w_bn_relu_rowdot_io`` (``_bf16``) on a contiguous fp32 or float16 (bfloat16) z (the vectors fp32); bn's running statistics
     move in place."""
     (M, C), dev = zc.shape, zc.device
     logit = torch.empty(M, dtype=torch.float32, device=dev)
     mean, invstd = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(2))
     rm, rv = (t.detach().to(torch.float32).contiguous() for t in (bn.running_mean, bn.running_var))
     ws = _head_ws(M, C, dev)
-    check(lib().p2w_bn_relu_rowdot_io(ptr(zc), _code(zc), C, ptr(gamma), ptr(beta), ptr(w), ptr(b), ptr(rm), ptr(rv), float(bn.momentum),
-                                      float(bn.eps), M, C, ptr(logit), ptr(mean), ptr(invstd), ptr(ws), ws.numel(), stream()), "bn_relu_rowdot")
+    tail = (ptr(gamma), ptr(beta), ptr(w), ptr(b), ptr(rm), ptr(rv), float(bn.momentum), float(bn.eps), M, C, ptr(logit), ptr(mean), ptr(invstd),
+            ptr(ws), ws.numel(), stream())
+    if zc.dtype == torch.bfloat16:
+        check(lib().p2w_bn_relu_rowdot_bf16(ptr(zc), C, *tail), "bn_relu_rowdot")
+    else:
+        check(lib().p2w_bn_relu_rowdot_io(ptr(zc), _code(zc), C, *tail), "bn_relu_rowdot")
     with torch.no_grad():
         for mine, theirs in ((rm, bn.running_mean), (rv, bn.running_var)):
             if mine.data_ptr() != theirs.data_ptr():
@@ -1170,14 +1193,17 @@ class _BnReluRowdot(torch.autograd.Function):
         dgamma, dbeta, dw = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(3))
         dbias = torch.empty(1, dtype=torch.float32, device=dev)
         ws = _head_ws(M, C, dev)
-        check(lib().p2w_bn_relu_rowdot_bwd_io(ptr(g), ptr(z), _code(z), C, ptr(gamma), ptr(beta), ptr(w), ptr(mean), ptr(invstd), M, C, ptr(dz), C,
-                                              ptr(dgamma), ptr(dbeta), ptr(dw), ptr(dbias), ptr(ws), ws.numel(), stream()),
-              "bn_relu_rowdot backward")
+        tail = (ptr(gamma), ptr(beta), ptr(w), ptr(mean), ptr(invstd), M, C, ptr(dz), C, ptr(dgamma), ptr(dbeta), ptr(dw), ptr(dbias), ptr(ws),
+                ws.numel(), stream())
+        if z.dtype == torch.bfloat16:
+            check(lib().p2w_bn_relu_rowdot_bwd_bf16(ptr(g), ptr(z), C, *tail), "bn_relu_rowdot backward")
+        else:
+            check(lib().p2w_bn_relu_rowdot_bwd_io(ptr(g), ptr(z), _code(z), C, *tail), "bn_relu_rowdot backward")
         return (*[gr.to(dt).reshape(shape) for gr, (dt, shape) in zip((dz, dgamma, dbeta, dw, dbias), ctx.like)], None)
 
 
 class _BnReluRowdotHalf(_BnReluRowdot):
-    """``_BnReluRowdot`` on a float16 ``z`` as it is (``half_io``): ``z`` itself is saved and ``dz`` is written in float16 by the kernel;
+    """``_BnReluRowdot`` on a float16 or bfloat16 ``z`` as it is (``half_io``): ``z`` itself is saved and ``dz`` is written in its dtype by the kernel;
     the logits and their gradient stay fp32."""
 
     @staticmethod
@@ -1204,7 +1230,7 @@ def bn_relu_rowdot(z, bn, weight, bias):
     in an order fixed by C alone (``include/p2w.h``); no floating-point atomics: the same bits on every run.  Running statistics
     (unbiased variance) and ``num_batches_tracked`` update as PyTorch's.  Computes in fp32 under autocast.  Under ``no_grad`` the
     forward runs, the statistics move and nothing is saved.  A float16 ``z`` with a gradient to track is read and saved as it is and
-    gets a float16 gradient from the kernel (``half_io``); the logits are fp32 either way.
+    gets a float16 gradient from the kernel (``half_io``; a bfloat16 ``z`` likewise, in bfloat16); the logits are fp32 either way.
 
     In eval mode this is the plain composition on the running statistics.  ``affine=False``, ``track_running_stats=False`` and
     ``momentum=None`` raise ``NotImplementedError``; fewer than two rows in training mode raise PyTorch's ``ValueError``."""

@@ -12,6 +12,11 @@ Deviations (route A-train): no per-step ``deepcopy(state_dict)``
 skips a step with non-finite gradients); no ``set_detect_anomaly``; no ``.item()`` per batch - ``EpochScores`` reads the device once
 per epoch; and the early-stop counter PERSISTS across epochs: the reference resets it to 0 at every epoch, so its ``>= 10`` can never
 fire - what is built is the intent its message documents (training accuracy decreased for 10 consecutive epochs).
+
+``args.amp`` (``train.py --amp``, ``"fp16"`` when absent) chooses the autocast dtype.  ``"fp16"`` is the loop above.  ``"bf16"`` runs
+autocast in bfloat16, which has fp32's exponent: the scaler is built disabled, so no loss scale exists and no step is lost to one;
+the norm that ``clip_grad_norm_`` returns is read once per step and a step whose norm is not finite is skipped and counted
+(``finish_step``), the count printed with the epoch line.  Parameters, history layout and checkpoints are the same in both modes.
 """
 from __future__ import annotations
 
@@ -82,14 +87,36 @@ def _save_best(model, stat, best, path):
     return best
 
 
+AMP_DTYPES = {"fp16": torch.float16, "bf16": torch.bfloat16}
+
+
+def finish_step(model, optimizer, scaler, amp="fp16"):
+    """What the loop does with the gradients of one batch, behind ``scaler.scale(loss).backward()``: unscale, clip to norm 1, step.
+    -> 1 where the step was skipped here, else 0.  ``"fp16"``: the enabled scaler finds non-finite gradients itself (its one host
+    read per step, inside ``scaler.step``) and skips without saying so: 0.  ``"bf16"``: the scaler is disabled and finds nothing, so
+    the clip's norm is read - the step's one host read - and, where it is not finite, ``optimizer.step()`` is not called: no
+    parameter and no optimizer state moves."""
+    scaler.unscale_(optimizer)
+    norm = torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=1.0)
+    if amp == "bf16" and not math.isfinite(float(norm)):
+        scaler.update()
+        return 1
+    scaler.step(optimizer)
+    scaler.update()
+    return 0
+
+
 def SemanticTraining(args):
     """``args``: the namespace of ``train.py`` - ``wdir``, ``model``, ``trfile`` / ``tefile`` (voxel directories), ``batch_size``,
     ``num_epochs``, ``checkpoints``, ``augmentation``, ``test``, ``tune``, ``stop_early``, ``wandb``, ``seed``, ``device_sample`` (absent
     or False: the reference's CPU draw of the training sample); ``args.C`` (not on the command line) is the network's width, 32 when
-    absent.  Returns the history array."""
+    absent; ``args.amp``, ``"fp16"`` (absent: the same) or ``"bf16"``.  Returns the history array."""
     if not torch.cuda.is_available():
         raise RuntimeError("SemanticTraining needs an MI355X (cuda) device; there is no CPU fallback")
     device = torch.device("cuda")
+    amp = getattr(args, "amp", "fp16")
+    if amp not in AMP_DTYPES:
+        raise ValueError(f"amp is 'fp16' or 'bf16', not {amp!r}")
     seed = int(getattr(args, "seed", 141190))                   # the reference's module-level torch.manual_seed(141190)
     torch.manual_seed(seed)
     wandb = None
@@ -150,7 +177,7 @@ def SemanticTraining(args):
             np.savetxt(os.path.join(model_dir, stem + "_history_backup.csv"), history)
 
     best_ba_train = best_f1_train = best_ba_test = best_f1_test = best_precision_test = 0.0
-    scaler = torch.amp.GradScaler("cuda", init_scale=512)
+    scaler = torch.amp.GradScaler("cuda", init_scale=512, enabled=amp == "fp16")
     history = None
     consec_decreases = 0
 
@@ -162,22 +189,20 @@ def SemanticTraining(args):
         if model.sampler is not None:
             model.sampler.set_epoch(epoch)
         scores = EpochScores(capacity=len(train_feed))
+        skipped = 0
         for data in train_feed:
             optimizer.zero_grad()
-            with torch.autocast("cuda", dtype=torch.float16):
+            with torch.autocast("cuda", dtype=AMP_DTYPES[amp]):
                 outputs = model(data)
                 loss, _ = criterion(outputs, data.y)
             scaler.scale(loss).backward()
-            scaler.unscale_(optimizer)
-            torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=1.0)
-            scaler.step(optimizer)
-            scaler.update()
+            skipped += finish_step(model, optimizer, scaler, amp)
             scores.add(outputs, data.y, loss)
         lr_scheduler.step()
         tr = scores.result()                                    # the epoch's one device-to-host copy
         lr = optimizer.param_groups[0]["lr"]
         print(f"Train  Lr {lr:.3g}  Lo {tr['loss']:.5f}  Ac {tr['balanced_accuracy']:.3f}  Pr {tr['precision']:.3f}  "
-              f"Re {tr['recall']:.3f}  F1 {tr['f1']:.3f}")
+              f"Re {tr['recall']:.3f}  F1 {tr['f1']:.3f}" + (f"  Skipped {skipped}" if amp == "bf16" else ""))
 
         te = None
         if test_feed is not None:

@@ -47,6 +47,9 @@ def build_parser():
     p.add_argument('--device_sample', action='store_true',
                    help="Draw each level's training sample on the GPU: the reference's law (a uniform half of the rows) from another "
                         "random stream, a function of (seed, epoch, step, level), so a seeded run samples other points than without it")
+    p.add_argument('--amp', choices=['fp16', 'bf16'], default='fp16',
+                   help="autocast dtype: fp16 with GradScaler(512) (the reference's loop), or bf16 without a loss scale, where a step "
+                        "whose gradient norm is not finite is skipped and counted")
     return p
 
 
