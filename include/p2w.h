@@ -913,6 +913,8 @@ int32_t p2w_bn_relu_rowdot_bwd(const float* g, const float* z, int32_t ldz, cons
  *   to  out and g         (p2w_bn_chain*, p2w_relu_bn*): P2W_F32, or equal to tz where tz is a 16-bit type
  *   tx  x and grad_x      (p2w_segment_max_*): P2W_F32 or P2W_F16; out, grad_out and arg stay fp32 / int32 (a maximum of widened
  *                         values is exact)
+ *   tz  z and dz          (p2w_relu_bn_max_io / _bwd_io): P2W_F32, P2W_F16 or P2W_BF16; g and out stay fp32, like ext, arg and every
+ *                         [C2] vector (an extremum of widened values is exact); both directions share p2w_relu_bn_max_ws_bytes
  * The four chain entry points take P2W_BF16.  p2w_bn_relu_rowdot_io / _bwd_io and p2w_segment_max_arg_io / _bwd_io have one code
  * each and answer 2 with P2W_EUNSUPPORTED like any other unknown code (tests/test_gpu_half_io.py: test_refusals_launch_nothing
  * asserts it of them); their bfloat16 instantiations are the four p2w_*_bf16 entry points below the _io ones.
@@ -948,6 +950,14 @@ int32_t p2w_segment_max_arg_io(const void* x, int32_t tx, int32_t ldx, int32_t F
                                int32_t* arg, p2w_stream_t stream);
 int32_t p2w_segment_max_bwd_io(const float* grad_out, int32_t ldg, const int32_t* arg, const int32_t* ptr, int32_t B, int32_t F,
                                void* grad_x, int32_t tx, int32_t ldx, int32_t n, p2w_stream_t stream);
+int32_t p2w_relu_bn_max_io(const void* z, int32_t tz, int32_t ldz, const int32_t* ptr, const float* gamma, const float* beta,
+                           float* running_mean, float* running_var, double momentum, double eps, int32_t E, int32_t M, int32_t C2,
+                           float* out, float* ext, int32_t* arg, float* mean, float* invstd, void* ws, size_t ws_bytes,
+                           p2w_stream_t stream);
+int32_t p2w_relu_bn_max_bwd_io(const float* g, const void* z, int32_t tz, int32_t ldz, const int32_t* ptr, const int32_t* arg,
+                               const float* ext, const float* mean, const float* invstd, const float* gamma, int32_t E, int32_t M,
+                               int32_t C2, void* dz, int32_t lddz, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
+                               p2w_stream_t stream);
 /* The head and the segment max on bfloat16 tensors: what their _io entry points would do for tz / tx = P2W_BF16 - the namesake's
  * arguments without the dtype code, z and dz (x and grad_x) bfloat16, everything else as above: the same launches, sums, workspace and
  * status codes, the widening load exact, every bfloat16 store one rounding to nearest even, 8-byte accesses where an 8-byte aligned

@@ -11,6 +11,10 @@
 // column by one lane in ascending row order, so the bits do not depend on V, on the grid or on the run: no floating-point atomics.
 //   sums:  fp64 partials per work item of P2W_BN_GROUP consecutive targets (rows ascending), then the items in ascending order
 //          (bnmax_reduce_kernel: the loads of 128 items are in flight together, one lane per column adds them in order).
+// Z and dZ also come in float16 and bfloat16 (p2w_relu_bn_max_io / _bwd_io; TZ = gr_half or gr_bf16, p2w_runsum.h): the element is
+// widened as it is loaded (exact) and dz rounded once as it is stored (gr_f2h / gr_f2b); V = 4 is then one 8-byte access on z / dz.
+// Everything between the load and the store is the fp32 code, so ext, arg, the sums and out are the fp32 entry point's on the
+// widened tensor bit for bit, and dz is its fp32 dz rounded once.
 #include "p2w_runsum.h"
 
 namespace {
@@ -26,8 +30,8 @@ __device__ __forceinline__ int bn_clamp(int v, int E) { return max(0, min(v, E))
 // them once in ascending order, adds y and y * y in fp64 (y * y is exact in fp64) and keeps the extremum of the current target with the
 // lowest row that holds it (strict comparison on an ascending walk).  ptr is clamped to [0, E] and made non-decreasing, so no bad
 // offset reaches an address.  A NaN in z counts as a non-positive value (y = 0).
-template <int V>
-__global__ __launch_bounds__(256) void bnmax_part_kernel(const float* __restrict__ z, int ldz, const int* __restrict__ ptr,
+template <int V, class TZ>
+__global__ __launch_bounds__(256) void bnmax_part_kernel(const TZ* __restrict__ z, int ldz, const int* __restrict__ ptr,
                                                          const float* __restrict__ gamma, int M, int E, int C2, int q, int items,
                                                          float* __restrict__ ext, int* __restrict__ arg, double* __restrict__ part) {
     const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -190,12 +194,12 @@ __global__ __launch_bounds__(256) void bnmax_apply_kernel(const float* __restric
 // row pass (W V columns), the block's 256 / W row lanes take rows rl, rl + 256 / W, ...; a row's target is found by bisection in LDS.
 //   xhat = (y - mean) invstd,  dy = ((g[e == arg] - k1) - xhat k2) (gamma invstd),  dz = z > 0 ? dy : 0          (fp32, no fma)
 // with k1 = dbeta / E and k2 = dgamma / E from the reduction.  Every element of the rows [ptr[0], ptr[M]) is written once.
-template <int V>
-__global__ __launch_bounds__(256) void bnmax_dz_kernel(const float* __restrict__ g, const float* __restrict__ z, int ldz,
+template <int V, class TZ>
+__global__ __launch_bounds__(256) void bnmax_dz_kernel(const float* __restrict__ g, const TZ* __restrict__ z, int ldz,
                                                        const int* __restrict__ ptr, const int* __restrict__ arg,
                                                        const float* __restrict__ mean, const float* __restrict__ invstd,
                                                        const float* __restrict__ gamma, const float* __restrict__ kq, int M, int E, int C2,
-                                                       int W, float* __restrict__ dz, int lddz) {
+                                                       int W, TZ* __restrict__ dz, int lddz) {
     __shared__ int sp[BN_G + 1];
     const int t0 = blockIdx.x * BN_G, nt = min(BN_G, M - t0);
     if (threadIdx.x == 0) {
@@ -256,10 +260,12 @@ extern "C" size_t p2w_relu_bn_max_ws_bytes(int32_t E, int32_t M, int32_t C2) {
     return p2w_ws_bytes([&](P2wArena& a) { bm_carve(a, M, C2); });
 }
 
-extern "C" int32_t p2w_relu_bn_max(const float* z, int32_t ldz, const int32_t* ptr, const float* gamma, const float* beta,
-                                   float* running_mean, float* running_var, double momentum, double eps, int32_t E, int32_t M, int32_t C2,
-                                   float* out, float* ext, int32_t* arg, float* mean, float* invstd, void* ws, size_t ws_bytes,
-                                   p2w_stream_t stream) {
+namespace {
+
+template <class TZ>
+int32_t bnmax_fwd_t(const TZ* z, int32_t ldz, const int32_t* ptr, const float* gamma, const float* beta, float* running_mean,
+                    float* running_var, double momentum, double eps, int32_t E, int32_t M, int32_t C2, float* out, float* ext, int32_t* arg,
+                    float* mean, float* invstd, void* ws, size_t ws_bytes, p2w_stream_t stream) {
     if (!bm_sizes_ok(E, M, C2) || ldz < C2 || !(eps >= 0.0) || !(momentum >= 0.0 && momentum <= 1.0)) return P2W_EINVAL;
     P2W_CHECK_PTR(z); P2W_CHECK_PTR(ptr); P2W_CHECK_PTR(gamma); P2W_CHECK_PTR(beta); P2W_CHECK_PTR(running_mean); P2W_CHECK_PTR(running_var);
     P2W_CHECK_PTR(out); P2W_CHECK_PTR(ext); P2W_CHECK_PTR(arg); P2W_CHECK_PTR(mean); P2W_CHECK_PTR(invstd); P2W_CHECK_PTR(ws);
@@ -267,13 +273,13 @@ extern "C" int32_t p2w_relu_bn_max(const float* z, int32_t ldz, const int32_t* p
     P2wArena arena(ws);
     const BmWs L = bm_carve(arena, M, C2);
     if (ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
-    const bool v4 = !(C2 & 3) && !(ldz & 3) && gr_al16(z) && gr_al16(gamma) && gr_al16(beta) && gr_al16(out) && gr_al16(ext) && gr_al16(arg) &&
+    const bool v4 = !(C2 & 3) && !(ldz & 3) && gr_alv(z) && gr_al16(gamma) && gr_al16(beta) && gr_al16(out) && gr_al16(ext) && gr_al16(arg) &&
                     gr_al16(mean) && gr_al16(invstd);
     hipStream_t s = p2w_s(stream);
     const int q = v4 ? C2 >> 2 : C2;
     const unsigned pb = (unsigned)(((long long)L.items * q + 255) / 256), ab = (unsigned)(((long long)M * q + 255) / 256);
-    if (v4) bnmax_part_kernel<4><<<pb, 256, 0, s>>>(z, ldz, ptr, gamma, M, E, C2, q, L.items, ext, arg, L.part);
-    else bnmax_part_kernel<1><<<pb, 256, 0, s>>>(z, ldz, ptr, gamma, M, E, C2, q, L.items, ext, arg, L.part);
+    if (v4) bnmax_part_kernel<4, TZ><<<pb, 256, 0, s>>>(z, ldz, ptr, gamma, M, E, C2, q, L.items, ext, arg, L.part);
+    else bnmax_part_kernel<1, TZ><<<pb, 256, 0, s>>>(z, ldz, ptr, gamma, M, E, C2, q, L.items, ext, arg, L.part);
     bnmax_reduce_kernel<<<p2w_cdiv(C2, RED_COLS), 256, 0, s>>>(L.part, L.items, C2, E, true, momentum, eps, mean, invstd, running_mean,
                                                                running_var, nullptr);
     if (v4) bnmax_apply_kernel<4><<<ab, 256, 0, s>>>(ext, arg, mean, invstd, gamma, beta, M, C2, q, out);
@@ -281,9 +287,10 @@ extern "C" int32_t p2w_relu_bn_max(const float* z, int32_t ldz, const int32_t* p
     return P2W_LAUNCH_STATUS();
 }
 
-extern "C" int32_t p2w_relu_bn_max_bwd(const float* g, const float* z, int32_t ldz, const int32_t* ptr, const int32_t* arg, const float* ext,
-                                       const float* mean, const float* invstd, const float* gamma, int32_t E, int32_t M, int32_t C2,
-                                       float* dz, int32_t lddz, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, p2w_stream_t stream) {
+template <class TZ>
+int32_t bnmax_bwd_t(const float* g, const TZ* z, int32_t ldz, const int32_t* ptr, const int32_t* arg, const float* ext, const float* mean,
+                    const float* invstd, const float* gamma, int32_t E, int32_t M, int32_t C2, TZ* dz, int32_t lddz, float* dgamma, float* dbeta,
+                    void* ws, size_t ws_bytes, p2w_stream_t stream) {
     if (!bm_sizes_ok(E, M, C2) || ldz < C2 || lddz < C2) return P2W_EINVAL;
     P2W_CHECK_PTR(g); P2W_CHECK_PTR(z); P2W_CHECK_PTR(ptr); P2W_CHECK_PTR(arg); P2W_CHECK_PTR(ext); P2W_CHECK_PTR(mean); P2W_CHECK_PTR(invstd);
     P2W_CHECK_PTR(gamma); P2W_CHECK_PTR(dz); P2W_CHECK_PTR(dgamma); P2W_CHECK_PTR(dbeta); P2W_CHECK_PTR(ws);
@@ -291,15 +298,64 @@ extern "C" int32_t p2w_relu_bn_max_bwd(const float* g, const float* z, int32_t l
     P2wArena arena(ws);
     const BmWs L = bm_carve(arena, M, C2);
     if (ws_bytes < arena.bytes()) return P2W_EWORKSPACE;
-    const bool v4 = !(C2 & 3) && !(ldz & 3) && !(lddz & 3) && gr_al16(g) && gr_al16(z) && gr_al16(arg) && gr_al16(ext) && gr_al16(mean) &&
-                    gr_al16(invstd) && gr_al16(gamma) && gr_al16(dz);
+    const bool v4 = !(C2 & 3) && !(ldz & 3) && !(lddz & 3) && gr_al16(g) && gr_alv(z) && gr_al16(arg) && gr_al16(ext) && gr_al16(mean) &&
+                    gr_al16(invstd) && gr_al16(gamma) && gr_alv(dz);
     hipStream_t s = p2w_s(stream);
     const int q = v4 ? C2 >> 2 : C2;
     const unsigned pb = (unsigned)(((long long)L.items * q + 255) / 256);
     if (v4) bnmax_bwd_part_kernel<4><<<pb, 256, 0, s>>>(g, ext, arg, mean, invstd, M, C2, q, L.items, L.part);
     else bnmax_bwd_part_kernel<1><<<pb, 256, 0, s>>>(g, ext, arg, mean, invstd, M, C2, q, L.items, L.part);
     bnmax_reduce_kernel<<<p2w_cdiv(C2, RED_COLS), 256, 0, s>>>(L.part, L.items, C2, E, false, 0.0, 0.0, dgamma, dbeta, nullptr, nullptr, L.kq);
-    if (v4) bnmax_dz_kernel<4><<<L.items, 256, 0, s>>>(g, z, ldz, ptr, arg, mean, invstd, gamma, L.kq, M, E, C2, run_row_lanes<4>(C2), dz, lddz);
-    else bnmax_dz_kernel<1><<<L.items, 256, 0, s>>>(g, z, ldz, ptr, arg, mean, invstd, gamma, L.kq, M, E, C2, run_row_lanes<1>(C2), dz, lddz);
+    if (v4) bnmax_dz_kernel<4, TZ><<<L.items, 256, 0, s>>>(g, z, ldz, ptr, arg, mean, invstd, gamma, L.kq, M, E, C2, run_row_lanes<4>(C2), dz, lddz);
+    else bnmax_dz_kernel<1, TZ><<<L.items, 256, 0, s>>>(g, z, ldz, ptr, arg, mean, invstd, gamma, L.kq, M, E, C2, run_row_lanes<1>(C2), dz, lddz);
     return P2W_LAUNCH_STATUS();
+}
+
+}  // namespace
+
+// z by its dtype code (include/p2w.h: P2W_F32, P2W_F16, P2W_BF16); an unknown code is refused before anything else is looked at
+extern "C" int32_t p2w_relu_bn_max_io(const void* z, int32_t tz, int32_t ldz, const int32_t* ptr, const float* gamma, const float* beta,
+                                      float* running_mean, float* running_var, double momentum, double eps, int32_t E, int32_t M, int32_t C2,
+                                      float* out, float* ext, int32_t* arg, float* mean, float* invstd, void* ws, size_t ws_bytes,
+                                      p2w_stream_t stream) {
+    if (tz == P2W_F32)
+        return bnmax_fwd_t(static_cast<const float*>(z), ldz, ptr, gamma, beta, running_mean, running_var, momentum, eps, E, M, C2, out, ext,
+                           arg, mean, invstd, ws, ws_bytes, stream);
+    if (tz == P2W_F16)
+        return bnmax_fwd_t(static_cast<const gr_half*>(z), ldz, ptr, gamma, beta, running_mean, running_var, momentum, eps, E, M, C2, out, ext,
+                           arg, mean, invstd, ws, ws_bytes, stream);
+    if (tz == P2W_BF16)
+        return bnmax_fwd_t(static_cast<const gr_bf16*>(z), ldz, ptr, gamma, beta, running_mean, running_var, momentum, eps, E, M, C2, out, ext,
+                           arg, mean, invstd, ws, ws_bytes, stream);
+    return P2W_EUNSUPPORTED;
+}
+
+extern "C" int32_t p2w_relu_bn_max(const float* z, int32_t ldz, const int32_t* ptr, const float* gamma, const float* beta,
+                                   float* running_mean, float* running_var, double momentum, double eps, int32_t E, int32_t M, int32_t C2,
+                                   float* out, float* ext, int32_t* arg, float* mean, float* invstd, void* ws, size_t ws_bytes,
+                                   p2w_stream_t stream) {
+    return p2w_relu_bn_max_io(z, P2W_F32, ldz, ptr, gamma, beta, running_mean, running_var, momentum, eps, E, M, C2, out, ext, arg, mean, invstd,
+                              ws, ws_bytes, stream);
+}
+
+extern "C" int32_t p2w_relu_bn_max_bwd_io(const float* g, const void* z, int32_t tz, int32_t ldz, const int32_t* ptr, const int32_t* arg,
+                                          const float* ext, const float* mean, const float* invstd, const float* gamma, int32_t E, int32_t M,
+                                          int32_t C2, void* dz, int32_t lddz, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
+                                          p2w_stream_t stream) {
+    if (tz == P2W_F32)
+        return bnmax_bwd_t(g, static_cast<const float*>(z), ldz, ptr, arg, ext, mean, invstd, gamma, E, M, C2, static_cast<float*>(dz), lddz,
+                           dgamma, dbeta, ws, ws_bytes, stream);
+    if (tz == P2W_F16)
+        return bnmax_bwd_t(g, static_cast<const gr_half*>(z), ldz, ptr, arg, ext, mean, invstd, gamma, E, M, C2, static_cast<gr_half*>(dz), lddz,
+                           dgamma, dbeta, ws, ws_bytes, stream);
+    if (tz == P2W_BF16)
+        return bnmax_bwd_t(g, static_cast<const gr_bf16*>(z), ldz, ptr, arg, ext, mean, invstd, gamma, E, M, C2, static_cast<gr_bf16*>(dz), lddz,
+                           dgamma, dbeta, ws, ws_bytes, stream);
+    return P2W_EUNSUPPORTED;
+}
+
+extern "C" int32_t p2w_relu_bn_max_bwd(const float* g, const float* z, int32_t ldz, const int32_t* ptr, const int32_t* arg, const float* ext,
+                                       const float* mean, const float* invstd, const float* gamma, int32_t E, int32_t M, int32_t C2,
+                                       float* dz, int32_t lddz, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, p2w_stream_t stream) {
+    return p2w_relu_bn_max_bwd_io(g, z, P2W_F32, ldz, ptr, arg, ext, mean, invstd, gamma, E, M, C2, dz, lddz, dgamma, dbeta, ws, ws_bytes, stream);
 }

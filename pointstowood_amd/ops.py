@@ -29,8 +29,8 @@ BatchNorm1d, ReLU, up to three times, and the residual add - computed from the G
 (``model.py:142-153``) trains through ``interp_add_relu`` (``csrc/p2w_fp.hip``: layer 0 hoisted behind the interpolation, the add and the
 ReLU in the interpolation's pass) and ``relu_bn`` (``csrc/p2w_bnchain.hip``: ReLU and training-mode BatchNorm1d from the GEMM's output).
 
-dtypes under autocast: ``bn_chain``, ``relu_bn``, ``bn_relu_rowdot`` and ``scatter_max`` / ``global_max_pool`` take a float16 or bfloat16
-tensor as it is, save that tensor and write a gradient of its dtype from the kernel (``half_io``, default True; False casts to fp32
+dtypes under autocast: ``bn_chain``, ``relu_bn``, ``relu_bn_max``, ``bn_relu_rowdot`` and ``scatter_max`` / ``global_max_pool`` take a float16 or
+bfloat16 tensor as it is, save that tensor and write a gradient of its dtype from the kernel (``half_io``, default True; False casts to fp32
 first - the same bits); ``bn_chain`` and ``relu_bn`` return that dtype on request (``out_dtype``), for a result that goes into ``F.linear``
 and nowhere else.
 """
@@ -144,9 +144,9 @@ def _wants_grad(x):
     return torch.is_grad_enabled() and x.requires_grad
 
 
-# float16 in and out of the training operators.  Under autocast the GEMMs around bn_chain, relu_bn, bn_relu_rowdot and scatter_max /
-# global_max_pool give and take float16.  True: with a gradient to track, a float16 z / x goes to the kernels as it is (the ``*_io``
-# entry points of include/p2w.h widen it as they load it), it is the tensor saved for the backward, and dz / grad_x is written in
+# float16 in and out of the training operators.  Under autocast the GEMMs around bn_chain, relu_bn, relu_bn_max, bn_relu_rowdot and
+# scatter_max / global_max_pool give and take float16.  True: with a gradient to track, a float16 z / x goes to the kernels as it is
+# (the ``*_io`` entry points of include/p2w.h widen it as they load it), it is the tensor saved for the backward, and dz / grad_x is written in
 # float16 by the kernel.  False: the route as it was - the big tensor is cast to fp32 first, that copy is saved, and the fp32
 # gradient is rounded in one more pass - launch for launch.  The two give the same bits everywhere: only the element type at the
 # loads and stores differs, and a float16 store is the one rounding the cast would have made.
@@ -391,15 +391,16 @@ def edge_layer1(P, Wg, pos_src, pos_dst, edge_index):
 
 
 def _relu_bn_max_forward(zc, gamma, beta, csr, M, bn):
-    """(out, ext, arg, mean, invstd) of ``p2w_relu_bn_max`` on fp32, contiguous inputs; bn's running statistics move in place."""
+    """(out, ext, arg, mean, invstd) of ``p2w_relu_bn_max_io`` on a contiguous fp32, float16 or bfloat16 z (the vectors fp32); bn's running
+    statistics move in place."""
     (E, C2), dev = zc.shape, zc.device
     out, ext = (torch.empty((M, C2), dtype=torch.float32, device=dev) for _ in range(2))
     arg = torch.empty((M, C2), dtype=torch.int32, device=dev)
     mean, invstd = (torch.empty(C2, dtype=torch.float32, device=dev) for _ in range(2))
     rm, rv = (t.detach().to(torch.float32).contiguous() for t in (bn.running_mean, bn.running_var))
     ws = torch.empty(ws_bytes("relu_bn_max", E, M, C2), dtype=torch.uint8, device=dev)
-    check(lib().p2w_relu_bn_max(ptr(zc), C2, ptr(csr), ptr(gamma), ptr(beta), ptr(rm), ptr(rv), float(bn.momentum), float(bn.eps), E, M, C2,
-                                ptr(out), ptr(ext), ptr(arg), ptr(mean), ptr(invstd), ptr(ws), ws.numel(), stream()), "relu_bn_max")
+    check(lib().p2w_relu_bn_max_io(ptr(zc), _code(zc), C2, ptr(csr), ptr(gamma), ptr(beta), ptr(rm), ptr(rv), float(bn.momentum), float(bn.eps),
+                                   E, M, C2, ptr(out), ptr(ext), ptr(arg), ptr(mean), ptr(invstd), ptr(ws), ws.numel(), stream()), "relu_bn_max")
     with torch.no_grad():
         for mine, theirs in ((rm, bn.running_mean), (rv, bn.running_var)):
             if mine.data_ptr() != theirs.data_ptr():
@@ -412,26 +413,49 @@ class _ReluBnMax(torch.autograd.Function):
     z, arg, ext, mean, invstd, the CSR and gamma - no [E, C2] tensor besides z itself."""
 
     @staticmethod
-    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, z, gamma, beta, csr, M, bn):
-        zc, gc = _f32c(z), _f32c(gamma)
+    def _forward(ctx, z, gamma, beta, csr, M, bn, keeps_half=False):
+        zc, gc = z.detach().contiguous() if keeps_half else _f32c(z), _f32c(gamma)
         out, ext, arg, mean, invstd = _relu_bn_max_forward(zc, gc, _f32c(beta), csr, M, bn)
         ctx.save_for_backward(zc, arg, ext, mean, invstd, csr, gc)
         ctx.dtypes = (z.dtype, gamma.dtype, beta.dtype)
         return out
 
     @staticmethod
-    @torch.amp.custom_bwd(device_type="cuda")
-    def backward(ctx, grad_out):
+    def _backward(ctx, grad_out):
         z, arg, ext, mean, invstd, csr, gamma = ctx.saved_tensors
         (E, C2), M, dev = z.shape, arg.shape[0], z.device
         g = _f32c(grad_out)
-        dz = torch.empty((E, C2), dtype=torch.float32, device=dev)
+        dz = torch.empty((E, C2), dtype=z.dtype, device=dev)
         dgamma, dbeta = (torch.empty(C2, dtype=torch.float32, device=dev) for _ in range(2))
         ws = torch.empty(ws_bytes("relu_bn_max", E, M, C2), dtype=torch.uint8, device=dev)
-        check(lib().p2w_relu_bn_max_bwd(ptr(g), ptr(z), C2, ptr(csr), ptr(arg), ptr(ext), ptr(mean), ptr(invstd), ptr(gamma), E, M, C2,
-                                        ptr(dz), C2, ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), stream()), "relu_bn_max backward")
+        check(lib().p2w_relu_bn_max_bwd_io(ptr(g), ptr(z), _code(z), C2, ptr(csr), ptr(arg), ptr(ext), ptr(mean), ptr(invstd), ptr(gamma), E, M,
+                                           C2, ptr(dz), C2, ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), stream()), "relu_bn_max backward")
         return dz.to(ctx.dtypes[0]), dgamma.to(ctx.dtypes[1]), dbeta.to(ctx.dtypes[2]), None, None, None
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, z, gamma, beta, csr, M, bn):
+        return _ReluBnMax._forward(ctx, z, gamma, beta, csr, M, bn)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_out):
+        return _ReluBnMax._backward(ctx, grad_out)
+
+
+class _ReluBnMaxHalf(_ReluBnMax):
+    """``_ReluBnMax`` on a float16 or bfloat16 ``z`` as it is (``half_io``): ``z`` itself is saved - no fp32 copy of it - the output stays
+    fp32 and ``dz`` is written in ``z``'s dtype by the kernel."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, csr, M, bn):
+        with _no_autocast():
+            return _ReluBnMax._forward(ctx, z, gamma, beta, csr, M, bn, keeps_half=True)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        with _no_autocast():
+            return _ReluBnMax._backward(ctx, grad_out)
 
 
 def _relu_bn_max_sorted(z, index, bn, M):
@@ -444,8 +468,9 @@ def _relu_bn_max_sorted(z, index, bn, M):
     if bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
     if torch.is_grad_enabled() and (z.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad):
-        return _ReluBnMax.apply(z, bn.weight, bn.bias, csr, M, bn)
-    return _relu_bn_max_forward(_f32c(z), _f32c(bn.weight), _f32c(bn.bias), csr, M, bn)[0]
+        return (_ReluBnMaxHalf if _keeps_half(z) else _ReluBnMax).apply(z, bn.weight, bn.bias, csr, M, bn)
+    zc = z.detach().contiguous() if _keeps_half(z) else _f32c(z)
+    return _relu_bn_max_forward(zc, _f32c(bn.weight), _f32c(bn.bias), csr, M, bn)[0]
 
 
 def relu_bn_max(z, index, bn, dim_size=None):
@@ -463,8 +488,10 @@ def relu_bn_max(z, index, bn, dim_size=None):
     a tied extremum sends its gradient to the lowest row (``scatter_max``'s rule).  Where ``gamma == 0`` the output does not depend on
     the winner; the gradient with respect to gamma is taken on the ``gamma >= 0`` side (through the maximum).  No floating-point
     atomics: the same bits on every run, the batch statistics included.  Saved for backward: ``z`` and [M, C] / [C] tensors only.
-    Computes in fp32 under autocast (a float16 ``z`` is cast first: one extra pass).  Under ``no_grad`` the forward runs, the running
-    statistics move, and nothing is saved.
+    Computes in fp32 under autocast and returns fp32.  A float16 or bfloat16 ``z`` is read as it is, is itself the tensor saved for the
+    backward and gets its gradient written in its dtype by the kernel (module switch ``half_io``, default True); with ``half_io`` False
+    it is cast to fp32 first: one extra pass each way and an fp32 copy saved, the same bits.  Under ``no_grad`` the forward runs, the
+    running statistics move, and nothing is saved.
 
     With ``bn.training`` false this is the composition itself, ``scatter_max(bn(relu(z)))`` on the running statistics: the kernels'
     backward carries the batch-statistics terms, so eval mode would need a second backward, not a flag.  ``affine=False``,
@@ -566,7 +593,8 @@ class PointNetConv(MessagePassing):
 
     ``fused_bn_max`` (default False; set it on the instance or the class): the training route computes everything after the layer-2
     GEMM with ``relu_bn_max`` instead of ReLU, BatchNorm1d and ``scatter_max`` one after the other - no [E, C2] tensor besides the
-    GEMM's output, the same bits on every run.  False leaves every launch and bit of the training route as it was; eval mode does
+    GEMM's output, the same bits on every run; under autocast that output goes to the kernels in its float16 or bfloat16 as it is
+    (``half_io``).  False leaves every launch and bit of the training route as it was; eval mode does
     not look at it."""
 
     fused_bn_max = False

@@ -11,8 +11,10 @@ operator route's modules - ``ops.PointNetConv``, ``ops.InvertedResidualBlock``, 
 (``bn_chain``, ``edge_layer1``, ``relu_bn``, ``interp_add_relu``, ``bn_relu_rowdot``: the same function as the plain statements,
 other roundings, the same bits on every run); False runs the reference's statements one by one on ``torch.nn`` modules and the
 plain ``ops`` callables - the baseline of an A/B comparison.  Assigning ``net.fused`` on a ``Net`` instance assigns it on every
-submodule that has the switch (``ops.FPModule`` included).  ``ops.PointNetConv.fused_bn_max`` is a separate switch and is not
-touched.  Gradients with respect to positions are not provided.
+submodule that has the switch (``ops.FPModule`` included).  ``ops.PointNetConv.fused_bn_max`` is a separate switch, default False:
+``net.fused`` does not touch it; ``trainer.set_fused_bn_max(net)`` (``train.py --fused_bn_max``) sets it on the three ``PointNetConv``
+instances of a ``Net``, whose layer-2 tail then runs through ``ops.relu_bn_max`` - under autocast on the GEMM's 16-bit output as it
+is.  Gradients with respect to positions are not provided.
 
 ``sampler`` (attribute of ``Net`` and ``SAModule``, default None): a ``DeviceSampler`` draws the three training samples on the GPU
 (``ops.random_subset``) as a function of (seed, epoch, step, level) in place of the reference's CPU ``randperm`` - the same law, a

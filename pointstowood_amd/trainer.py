@@ -106,11 +106,25 @@ def finish_step(model, optimizer, scaler, amp="fp16"):
     return 0
 
 
+def set_fused_bn_max(model, on=True):
+    """``fused_bn_max = on`` on every ``ops.PointNetConv`` instance of ``model`` - on the instances, so the class default (False) and
+    every other model stay as they are.  -> the number of layers set."""
+    n = 0
+    for m in model.modules():
+        if isinstance(m, _train.ops.PointNetConv):
+            m.fused_bn_max = bool(on)
+            n += 1
+    return n
+
+
 def SemanticTraining(args):
     """``args``: the namespace of ``train.py`` - ``wdir``, ``model``, ``trfile`` / ``tefile`` (voxel directories), ``batch_size``,
     ``num_epochs``, ``checkpoints``, ``augmentation``, ``test``, ``tune``, ``stop_early``, ``wandb``, ``seed``, ``device_sample`` (absent
     or False: the reference's CPU draw of the training sample); ``args.C`` (not on the command line) is the network's width, 32 when
-    absent; ``args.amp``, ``"fp16"`` (absent: the same) or ``"bf16"``.  Returns the history array."""
+    absent; ``args.amp``, ``"fp16"`` (absent: the same) or ``"bf16"``; ``args.fused_bn_max`` (``train.py --fused_bn_max``; absent or
+    False: nothing changes): every ``ops.PointNetConv`` of the model runs ReLU, BatchNorm1d and the segment max behind its layer-2
+    GEMM as ``ops.relu_bn_max``, on the GEMM's float16 / bfloat16 output as it is - the same function as the three statements, other
+    roundings, the same bits on every run, the same ``state_dict``.  Returns the history array."""
     if not torch.cuda.is_available():
         raise RuntimeError("SemanticTraining needs an MI355X (cuda) device; there is no CPU fallback")
     device = torch.device("cuda")
@@ -132,6 +146,8 @@ def SemanticTraining(args):
     print("Model contains", sum(p.numel() for p in model.parameters()), " parameters")
     if getattr(args, "device_sample", False):                   # the training samples drawn on the GPU (train.DeviceSampler)
         model.sampler = _train.DeviceSampler(seed)
+    if getattr(args, "fused_bn_max", False):                    # relu_bn_max behind every PointNetConv's layer-2 GEMM
+        set_fused_bn_max(model)
 
     train_feed = TrainingFeed(TrainingSet(args.trfile, device), args.batch_size, shuffle=True, drop_last=True,
                               augmentation=args.augmentation, mode="train", seed=seed)

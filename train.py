@@ -10,7 +10,9 @@ finds that folder by searching its own checkout's name in the working directory;
 directory).  ``--seed`` seeds the initialisation, the network's training sample and the feed (default: the reference's 141190).
 
 The loop is ``pointstowood_amd.trainer.SemanticTraining``: the whole set lives on the GPU, and every batch is gathered, augmented,
-centred and collated there (``pointstowood_amd.feed``).
+centred and collated there (``pointstowood_amd.feed``).  ``--fused_bn_max`` (default off) sets ``fused_bn_max`` on every
+``ops.PointNetConv`` of the model: ReLU, training-mode BatchNorm and the segment max behind the layer-2 GEMM run as ``ops.relu_bn_max``,
+which under ``--amp`` of either dtype reads the GEMM's 16-bit output and writes its gradient in that dtype.
 """
 from __future__ import annotations
 
@@ -50,6 +52,10 @@ def build_parser():
     p.add_argument('--amp', choices=['fp16', 'bf16'], default='fp16',
                    help="autocast dtype: fp16 with GradScaler(512) (the reference's loop), or bf16 without a loss scale, where a step "
                         "whose gradient norm is not finite is skipped and counted")
+    p.add_argument('--fused_bn_max', action='store_true',
+                   help="Run ReLU, BatchNorm and the max behind every PointNetConv's layer-2 GEMM as one fused operator "
+                        "(ops.relu_bn_max) that reads the GEMM's 16-bit output as it is: less memory traffic and a lower peak, "
+                        "other roundings than the three statements")
     return p
 
 
