@@ -428,6 +428,77 @@ size_t p2w_random_subset_ws_size(int64_t n);
 int32_t p2w_random_subset(int64_t n, int64_t k, uint64_t seed, uint32_t c1, uint32_t c2, const uint32_t* keys, int64_t* idx_out,
                           uint32_t* keys_out, void* ws, size_t ws_bytes, p2w_stream_t stream);
 
+/* The optimiser step behind backward(): unscale, clip to a global norm, AdamW and the loss-scale law, decided and applied on the device -
+ * what the reference's loop (pointstowood/src/trainer.py:196-204) composes from scaler.unscale_, clip_grad_norm_(max_norm),
+ * scaler.step(AdamW(amsgrad=False, maximize=False)) and scaler.update(), as ONE documented fp32 operation order.
+ * In : tensors[T] = a HOST array of records of DEVICE pointers (p, g, m, v: n fp32 elements each, contiguous; an entry with n = 0 is
+ *      skipped and its pointers are not looked at); hyper = a HOST structure, read during the call; state = the DEVICE record the caller
+ *      owns and keeps across steps (before the first step: scale = the loss scale that multiplied the loss, or 1; all else 0).
+ * Out: p, m, v updated in place (or untouched), the record rewritten.  g is only read.
+ * Work: a chunk is P2W_OPTIM_CHUNK consecutive elements of ONE tensor (256 threads, 16 elements each; a tensor's last chunk may be
+ *      short), numbered through the non-empty tensors in table order.  The table travels BY VALUE in the kernel arguments, one launch
+ *      per group of at most P2W_OPTIM_GROUP non-empty tensors: nothing is uploaded, so the table may be rebuilt at every step.  With T'
+ *      non-empty tensors a step is 2 ceil(T' / P2W_OPTIM_GROUP) + 1 launches:
+ *   norm      inv_scale = fl32(1 / (double)state.scale) (scaling off: 1).  Per chunk: sum of (double)u (double)u, u = fl32(g * inv_scale),
+ *             in fp64 (each square exact): thread t takes elements 1024 r + 4 t + j (r, j = 0 .. 3) in ascending order, the 64 lanes of
+ *             a wave are added by a xor-shuffle tree (offsets 32, 16, .. 1), the 4 waves in wave order -> the chunk's word of ws.
+ *   finalise  one workgroup: thread t adds the words t, t + 256, .. ascending, same tree, same wave order -> sumsq.
+ *             found_inf = !isfinite(sumsq): exact, since an fp32 square is below 1.2e77 and 2^40 of them cannot overflow fp64, while an
+ *             inf or a NaN anywhere in g reaches the sum.  norm = fl32(sqrt(sumsq)); coef = fminf(1, fl32(max_norm) / (norm + 1e-6f)).
+ *             found_inf : scale *= fl32(backoff_factor), growth_tracker = 0, skipped += 1; t and the seven scalars keep their values.
+ *             otherwise : t += 1, growth_tracker += 1, and where it reaches growth_interval: scale *= fl32(growth_factor),
+ *                         growth_tracker = 0.  Scaling off: scale = 1, the counters move the same way.
+ *             The seven scalars, each evaluated in fp64 (the device's double pow) and rounded to fp32 ONCE: decay = 1 - lr weight_decay,
+ *             omb1 = 1 - beta1, beta2, omb2 = 1 - beta2, step_size = lr / (1 - beta1^t), rsb2 = 1 / sqrt(1 - beta2^t), eps.
+ *   update    every workgroup reads the record; on found_inf it returns without a store.  Otherwise per element, in fp32:
+ *                 u  = g * inv_scale          gc = u * coef
+ *                 p1 = p * decay
+ *                 m' = m + (gc - m) * omb1
+ *                 v' = v * beta2 + (omb2 * gc) * gc
+ *                 d  = sqrt(v') * rsb2 + eps
+ *                 p' = p1 - step_size * (m' / d)
+ *             every operation one correctly rounded IEEE operation (no contraction, no fma anywhere in the step; correctly rounded
+ *             square root and division; subnormals kept), so a CPU replay in fp32 reproduces the bits.
+ * 16 bytes per access where a tensor's addresses allow (norm: g; update: p, g, m and v together), else 4: the same element-to-thread map
+ * and the same bits.  No memset, no atomics, no host synchronisation, no host read, no wait between workgroups: equal inputs give equal
+ * bits whatever ws held.
+ * 0 <= T <= P2W_OPTIM_MAX_TENSORS, every n >= 0, at most 2^40 elements in all; lr, eps, weight_decay, max_norm finite and >= 0,
+ * 0 <= beta1, beta2 < 1, growth_factor > 1 and finite, 0 < backoff_factor < 1, growth_interval >= 1, scaling 0 or 1 (P2W_EINVAL).
+ * tensors (T > 0), hyper, and - where there is an element - state, ws and the four pointers of every non-empty entry are required
+ * (P2W_ENULL); state and ws 16-byte, tensor pointers 4-byte aligned (P2W_EALIGN); ws: p2w_clip_adamw_ws_size(numel, T) bytes, 8 per chunk
+ * (0 = bad sizes; too small: P2W_EWORKSPACE).  T = 0 or every n = 0: P2W_OK, nothing launched, nothing written.  A refused call
+ * launches nothing. */
+#define P2W_OPTIM_CHUNK 4096
+#define P2W_OPTIM_GROUP 32
+#define P2W_OPTIM_MAX_TENSORS 4096
+typedef struct p2w_optim_tensor {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    int64_t n;
+} p2w_optim_tensor;
+typedef struct p2w_optim_hyper {
+    double lr, beta1, beta2, eps, weight_decay, max_norm, growth_factor, backoff_factor;
+    int32_t growth_interval;
+    int32_t scaling; /* 0: no loss scale (the scale is 1 and stays 1) */
+} p2w_optim_hyper;
+typedef struct p2w_optim_state {
+    double sumsq;           /* of the unscaled gradients */
+    float norm, coef;
+    float inv_scale;        /* the one this step used */
+    float scale;            /* the loss scale of the NEXT step */
+    int32_t found_inf;      /* 1: this step was skipped */
+    int32_t growth_tracker;
+    int64_t t;              /* steps applied */
+    int64_t skipped;        /* steps skipped */
+    float decay, omb1, beta2, omb2, step_size, rsb2, eps;
+    int32_t reserved;       /* 80-byte record */
+} p2w_optim_state;
+size_t p2w_clip_adamw_ws_size(const int64_t* numel, int32_t T);
+int32_t p2w_clip_adamw(const p2w_optim_tensor* tensors, int32_t T, const p2w_optim_hyper* hyper, p2w_optim_state* state, void* ws,
+                       size_t ws_bytes, p2w_stream_t stream);
+
 /* PointCloudClassifier.compute_labels (predicter.py:112-127) over a neighbour table nbr[n,k] (indices into pred /
  * prob, deg[i] valid entries): pwood_out = median of the neighbours' probabilities (np.median: mean of the two middle
  * values for an even count); label_out: any_wood != 1 -> 1 if any neighbour's prediction > any_wood else 0;

@@ -27,6 +27,21 @@ class BnStage(C.Structure):                                     # include/p2w.h 
                 ("momentum", C.c_double), ("eps", C.c_double), ("relu", _i32)]
 
 
+class OptimTensor(C.Structure):                                 # include/p2w.h p2w_optim_tensor (a HOST array of device pointers)
+    _fields_ = [("p", _vp), ("g", _vp), ("m", _vp), ("v", _vp), ("n", C.c_int64)]
+
+
+class OptimHyper(C.Structure):                                  # include/p2w.h p2w_optim_hyper
+    _fields_ = [(k, C.c_double) for k in ("lr", "beta1", "beta2", "eps", "weight_decay", "max_norm", "growth_factor", "backoff_factor")] + \
+               [("growth_interval", _i32), ("scaling", _i32)]
+
+
+class OptimState(C.Structure):                                  # include/p2w.h p2w_optim_state (the 80-byte DEVICE record)
+    _fields_ = [("sumsq", C.c_double), ("norm", _f32), ("coef", _f32), ("inv_scale", _f32), ("scale", _f32), ("found_inf", _i32),
+                ("growth_tracker", _i32), ("t", C.c_int64), ("skipped", C.c_int64), ("decay", _f32), ("omb1", _f32), ("beta2", _f32),
+                ("omb2", _f32), ("step_size", _f32), ("rsb2", _f32), ("eps", _f32), ("reserved", _i32)]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/p2w.h
 SEARCH_X_INDEX_IN_W, SEARCH_Q_ROW_IN_W, SEARCH_BOX = 1, 2, 4   # include/p2w.h P2W_SEARCH_*
 PREC_F16X3, PREC_F16, PREC_BF16 = 0, 1, 2                      # include/p2w.h P2W_PREC_*
@@ -43,6 +58,7 @@ BN_GROUP = 16                                                                   
 BN_CHAIN_MAX, BN_CHAIN_ROWS = 3, 32                                                                # P2W_BN_CHAIN_*
 FEED_CHUNK, FEED_STREAM = 256, 0x50325746                                                          # P2W_FEED_*
 SAMPLE_STREAM, SAMPLE_TILE, SAMPLE_N_MAX = 0x50325753, 1024, 1 << 24                               # P2W_SAMPLE_*
+OPTIM_CHUNK, OPTIM_GROUP, OPTIM_MAX_TENSORS = 4096, 32, 4096                                       # P2W_OPTIM_*
 F32, F16, BF16 = 0, 1, 2                                                                           # P2W_F32, P2W_F16, P2W_BF16
 
 SIGNATURES = {
@@ -98,6 +114,8 @@ SIGNATURES = {
                               _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "p2w_random_subset_ws_size": (_sz, [C.c_int64]),
     "p2w_random_subset": (_i32, [C.c_int64, C.c_int64, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "p2w_clip_adamw_ws_size": (_sz, [_vp, _i32]),
+    "p2w_clip_adamw": (_i32, [C.POINTER(OptimTensor), _i32, C.POINTER(OptimHyper), _vp, _vp, _sz, _vp]),
     "p2w_tile_bbox": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "p2w_tile_bbox_count": (_i32, [_i32, _i32]),
     "p2w_stem": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp]),

@@ -19,7 +19,7 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libp2w_gfx950.so")
 SOURCES = ["p2w_geom.hip", "p2w_feat.hip", "p2w_feat_h1.hip", "p2w_cluster.hip", "p2w_pathlen.hip", "p2w_eval.hip",
            "p2w_grad.hip", "p2w_loss.hip", "p2w_edge.hip", "p2w_bnmax.hip", "p2w_bnchain.hip", "p2w_fp.hip", "p2w_head.hip",
-           "p2w_feed.hip", "p2w_sample.hip"]
+           "p2w_feed.hip", "p2w_sample.hip", "p2w_optim.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          *os.environ.get("P2W_EXTRA_CFLAGS", "").split(),      # diagnostic builds, e.g. -DP2W_SLAB_PROFILE
          "-I", INCLUDE]

@@ -17,6 +17,10 @@ fire - what is built is the intent its message documents (training accuracy decr
 autocast in bfloat16, which has fp32's exponent: the scaler is built disabled, so no loss scale exists and no step is lost to one;
 the norm that ``clip_grad_norm_`` returns is read once per step and a step whose norm is not finite is skipped and counted
 (``finish_step``), the count printed with the epoch line.  Parameters, history layout and checkpoints are the same in both modes.
+
+``args.fused_step`` (``train.py --fused_step``, off when absent) replaces ``finish_step`` and both optimisers by ``optim.ClipAdamW``:
+unscale, clip, AdamW and the loss-scale law as one fused operator that decides skip-or-apply on the device (loss scale 512 under
+``"fp16"``, none under ``"bf16"``).  The step then reads nothing back in either mode; the skipped count comes with the epoch's scores.
 """
 from __future__ import annotations
 
@@ -124,7 +128,9 @@ def SemanticTraining(args):
     absent; ``args.amp``, ``"fp16"`` (absent: the same) or ``"bf16"``; ``args.fused_bn_max`` (``train.py --fused_bn_max``; absent or
     False: nothing changes): every ``ops.PointNetConv`` of the model runs ReLU, BatchNorm1d and the segment max behind its layer-2
     GEMM as ``ops.relu_bn_max``, on the GEMM's float16 / bfloat16 output as it is - the same function as the three statements, other
-    roundings, the same bits on every run, the same ``state_dict``.  Returns the history array."""
+    roundings, the same bits on every run, the same ``state_dict``; ``args.fused_step`` (``train.py --fused_step``; absent or False:
+    nothing changes): the optimiser is ``optim.ClipAdamW`` with the same ``lr`` and ``weight_decay`` and the loop is
+    ``optimizer.scale(loss).backward(); optimizer.step()`` - same history layout, same checkpoints.  Returns the history array."""
     if not torch.cuda.is_available():
         raise RuntimeError("SemanticTraining needs an MI355X (cuda) device; there is no CPU fallback")
     device = torch.device("cuda")
@@ -161,12 +167,20 @@ def SemanticTraining(args):
 
     criterion = Poly1FocalLoss(reduction="mean", gamma=2.0, alpha=None, label_smoothing=0.1)
     params = [p for p in model.parameters() if p.requires_grad]
+    fused_step = bool(getattr(args, "fused_step", False))
+    if fused_step:
+        from .optim import ClipAdamW
+
+        def make_optimizer(params, lr, weight_decay):
+            return ClipAdamW(params, lr=lr, weight_decay=weight_decay, max_norm=1.0, loss_scale=512.0 if amp == "fp16" else None)
+    else:
+        make_optimizer = torch.optim.AdamW
     if args.tune:
-        optimizer = torch.optim.AdamW(params, lr=1e-6, weight_decay=1e-2)
+        optimizer = make_optimizer(params, lr=1e-6, weight_decay=1e-2)
         lr_scheduler = CosineAnnealingWarmupRestarts(optimizer, first_cycle_steps=args.num_epochs // 5, cycle_mult=1.0, max_lr=1e-6,
                                                      min_lr=1e-8, warmup_steps=5, gamma=0.5)
     else:
-        optimizer = torch.optim.AdamW(params, lr=1e-4, weight_decay=1e-2)
+        optimizer = make_optimizer(params, lr=1e-4, weight_decay=1e-2)
         lr_scheduler = torch.optim.lr_scheduler.OneCycleLR(optimizer, max_lr=1e-4, total_steps=args.num_epochs, pct_start=0.05,
                                                            anneal_strategy="cos", div_factor=100)
 
@@ -196,6 +210,7 @@ def SemanticTraining(args):
     scaler = torch.amp.GradScaler("cuda", init_scale=512, enabled=amp == "fp16")
     history = None
     consec_decreases = 0
+    skipped_before = 0                                          # (fused_step) the device's count at the end of the last epoch
 
     for epoch in range(1, args.num_epochs + 1):
         model.train()
@@ -211,14 +226,21 @@ def SemanticTraining(args):
             with torch.autocast("cuda", dtype=AMP_DTYPES[amp]):
                 outputs = model(data)
                 loss, _ = criterion(outputs, data.y)
-            scaler.scale(loss).backward()
-            skipped += finish_step(model, optimizer, scaler, amp)
+            if fused_step:
+                optimizer.scale(loss).backward()
+                optimizer.step()
+            else:
+                scaler.scale(loss).backward()
+                skipped += finish_step(model, optimizer, scaler, amp)
             scores.add(outputs, data.y, loss)
         lr_scheduler.step()
         tr = scores.result()                                    # the epoch's one device-to-host copy
         lr = optimizer.param_groups[0]["lr"]
+        if fused_step:                                          # read with the scores: the steps this epoch skipped
+            total = optimizer.read()["skipped"]
+            skipped, skipped_before = total - skipped_before, total
         print(f"Train  Lr {lr:.3g}  Lo {tr['loss']:.5f}  Ac {tr['balanced_accuracy']:.3f}  Pr {tr['precision']:.3f}  "
-              f"Re {tr['recall']:.3f}  F1 {tr['f1']:.3f}" + (f"  Skipped {skipped}" if amp == "bf16" else ""))
+              f"Re {tr['recall']:.3f}  F1 {tr['f1']:.3f}" + (f"  Skipped {skipped}" if amp == "bf16" or fused_step else ""))
 
         te = None
         if test_feed is not None:

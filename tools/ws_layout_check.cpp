@@ -33,6 +33,7 @@ static std::vector<Region> g_regions;
 #include "../pointstowood_amd/csrc/p2w_head.hip"
 #include "../pointstowood_amd/csrc/p2w_feed.hip"
 #include "../pointstowood_amd/csrc/p2w_sample.hip"
+#include "../pointstowood_amd/csrc/p2w_optim.hip"
 
 static int g_fail = 0, g_runs = 0;
 
@@ -77,6 +78,7 @@ int main() {
         check("grow_carve", n, 0, 0, [&](P2wArena& a) { grow_carve(a, n); });
         check("lf_carve", n, 0, 0, [&](P2wArena& a) { lf_carve(a, n); });
         check("sm_carve", n, 0, 0, [&](P2wArena& a) { sm_carve(a, n); });
+        check("op_carve", n, 0, 0, [&](P2wArena& a) { op_carve(a, n); });
         for (int flags : {0, (int)P2W_SA_PACK8}) check("sa_conv_carve", n, flags, 0, [&](P2wArena& a) { sa_conv_carve(a, (long)n, flags); });
         for (long long t : {0ll, 1ll, 257ll, 4097ll, 1ll << 22}) {
             check("tk_carve", n, t, 0, [&](P2wArena& a) { tk_carve(a, i, t); });

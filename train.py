@@ -12,7 +12,8 @@ directory).  ``--seed`` seeds the initialisation, the network's training sample 
 The loop is ``pointstowood_amd.trainer.SemanticTraining``: the whole set lives on the GPU, and every batch is gathered, augmented,
 centred and collated there (``pointstowood_amd.feed``).  ``--fused_bn_max`` (default off) sets ``fused_bn_max`` on every
 ``ops.PointNetConv`` of the model: ReLU, training-mode BatchNorm and the segment max behind the layer-2 GEMM run as ``ops.relu_bn_max``,
-which under ``--amp`` of either dtype reads the GEMM's 16-bit output and writes its gradient in that dtype.
+which under ``--amp`` of either dtype reads the GEMM's 16-bit output and writes its gradient in that dtype.  ``--fused_step`` (default
+off) runs unscale, clip, AdamW and the loss-scale law of every step as one fused operator (``pointstowood_amd.optim.ClipAdamW``).
 """
 from __future__ import annotations
 
@@ -56,6 +57,10 @@ def build_parser():
                    help="Run ReLU, BatchNorm and the max behind every PointNetConv's layer-2 GEMM as one fused operator "
                         "(ops.relu_bn_max) that reads the GEMM's 16-bit output as it is: less memory traffic and a lower peak, "
                         "other roundings than the three statements")
+    p.add_argument('--fused_step', action='store_true',
+                   help="Run unscale, clip_grad_norm_(1.0), AdamW and the loss-scale update of every step as one fused operator "
+                        "(optim.ClipAdamW): skip-or-apply is decided on the GPU and no step reads the device; a documented fp32 "
+                        "operation order, other roundings than torch's AdamW; the skipped count is printed with every epoch")
     return p
 
 
