@@ -428,6 +428,55 @@ size_t p2w_random_subset_ws_size(int64_t n);
 int32_t p2w_random_subset(int64_t n, int64_t k, uint64_t seed, uint32_t c1, uint32_t c2, const uint32_t* keys, int64_t* idx_out,
                           uint32_t* keys_out, void* ws, size_t ws_bytes, p2w_stream_t stream);
 
+/* The voxeliser's cap: every one of S segments of a row space of n rows is cut down to k rows in ONE call - the reference's per-voxel
+ * torch.multinomial(weight[voxel], max_pts) / torch.randint(len, (max_pts,)) (pointstowood/src/preprocessing.py:116-120) as a function of
+ * (seed, c1, c2) and of each segment's own (row_id, weight) pairs, from the feed's generator and not from the reference's random stream.
+ * In : seg_start[S], seg_count[S] int64 = disjoint segments in ascending order; weight[n] float32 (optional: NULL); row_id[n] int64
+ *      (optional: NULL = the row's own position) = what the generator knows a row by; keys[n] uint32 (optional: NULL) = the key of every
+ *      row, used IN PLACE of the generator and the weights.  Out: idx_out[S][k] int64 = positions in the row space; keys_out[n] uint32
+ *      (optional: NULL) = the key of every row of every segment (other rows are not written).  All DEVICE memory.
+ * Weighted mode (weight or keys given): the law of multinomial without replacement - successive sampling, each draw proportional to the
+ * weights of the rows still there - as an exponential race (Efraimidis and Spirakis 2006: the k smallest of independent Exp(w_i)):
+ *   w0_i   = word 0 of Philox4x32-10 with counter (row_id_i & 0xffffffff, c1, c2, P2W_CAP_STREAM), key (seed & 0xffffffff, seed >> 32);
+ *   u_i    = (w0_i + 0.5) 2^-32, in (0, 1);
+ *   key_i  = fl32(-log(u_i) / w_i): logarithm (the device's double log) and division in float64, rounded ONCE to float32; positive or
+ *            +inf, so the bit pattern orders as an unsigned integer and is the selection's 32-bit key;
+ *            0xFFFFFFFF where w_i is not a finite positive number: behind every valid key, +inf included, taken only when valid rows run
+ *            out;
+ *   segment s keeps the k rows of its range that are smallest in (key_i, position i); idx_out[s][0..k) = those positions, ascending.
+ *   count_s <= k: all its rows, then -1 up to k.
+ * Equal keys are ordered by position, as in p2w_random_subset: with T the k-th smallest key of a segment, of the rows whose key is T the
+ * lowest positions are taken.  A float32 key has 24 significant bits, so T stands for an interval of relative width 2^-23 at most; the
+ * race's keys have density sum_i w_i exp(-w_i t) <= k / T there (about k of the w_i T add up to the k rows below T), so a second row
+ * shares the boundary key with probability of order k 2^-23 per segment (2e-3 at k = 16 384), and only then is the lower position
+ * preferred: inclusion probabilities differ from the law's by that order at most.
+ * Replacement mode (weight == NULL and keys == NULL): k uniform draws WITH replacement, in draw order j = 0 .. k-1:
+ *   idx_out[s][j] = start_s + floor(w0 count_s / 2^32), w0 = word 0 at counter (j, row_id[start_s] & 0xffffffff, c2, P2W_CAP_STREAM ^ 1)
+ *   (c1 is not used).  Integer arithmetic only; a position's probability differs from 1 / count by at most count 2^-32, relative.
+ *   count_s = 0: -1 throughout.  One launch; keys_out and ws are not looked at.
+ * Starts are clamped to [0, n] and counts to [0, n - start]: nothing outside the row space is read, whatever the two arrays hold.
+ * Segments that overlap get unspecified rows of their own ranges (disjoint segments have at most n / P2W_SAMPLE_TILE + S tiles, which is
+ * the launch grid).
+ * 0 <= n <= P2W_CAP_N_MAX, 0 <= S <= P2W_CAP_S_MAX, 1 <= k <= P2W_CAP_N_MAX, S k <= P2W_CAP_OUT_MAX (P2W_EINVAL; p2w_cap_subset_ws_size
+ * returns 0 for an n or S outside).  S = 0: P2W_OK, nothing launched, nothing written.  seg_start, seg_count, idx_out and - in weighted
+ * mode - ws required (P2W_ENULL); ws 16-byte, the int64 arrays 8-byte, the 32-bit arrays 4-byte aligned (P2W_EALIGN); ws:
+ * p2w_cap_subset_ws_size(n, S) bytes (4 per row, four 256-bin histograms and a control record per segment, S + 1 tile offsets, two
+ * counters per tile of P2W_SAMPLE_TILE rows, n / P2W_SAMPLE_TILE + S + 1 tiles, and the two scans' tile sums; too small:
+ * P2W_EWORKSPACE).  A refused call launches nothing.
+ * The selection is p2w_random_subset's (radix select of the k-th key over four 8-bit digits, stable compaction), with one histogram set
+ * per segment; a segment's tiles are the P2W_SAMPLE_TILE-row pieces of its own range, numbered through all segments by a scan on the
+ * device, so one large segment is spread over as many workgroups as it has tiles.  9 launches (11 above 4095 segments, 2 more where
+ * 2 (n / P2W_SAMPLE_TILE + S + 1) > 4096), whatever S.  No memset, no host synchronisation, no host read, no wait between workgroups;
+ * the atomics are integer additions to histogram bins, no floating-point atomics: the same bits on every run, whatever ws held. */
+#define P2W_CAP_STREAM 0x50325743u /* "P2WC"; replacement mode uses P2W_CAP_STREAM ^ 1 */
+#define P2W_CAP_N_MAX ((int64_t)1 << 30)
+#define P2W_CAP_S_MAX ((int64_t)1 << 20)
+#define P2W_CAP_OUT_MAX ((int64_t)1 << 38)
+size_t p2w_cap_subset_ws_size(int64_t n, int64_t S);
+int32_t p2w_cap_subset(int64_t n, const int64_t* seg_start, const int64_t* seg_count, int64_t S, int64_t k, const float* weight,
+                       const int64_t* row_id, uint64_t seed, uint32_t c1, uint32_t c2, const uint32_t* keys, int64_t* idx_out,
+                       uint32_t* keys_out, void* ws, size_t ws_bytes, p2w_stream_t stream);
+
 /* The optimiser step behind backward(): unscale, clip to a global norm, AdamW and the loss-scale law, decided and applied on the device -
  * what the reference's loop (pointstowood/src/trainer.py:196-204) composes from scaler.unscale_, clip_grad_norm_(max_norm),
  * scaler.step(AdamW(amsgrad=False, maximize=False)) and scaler.update(), as ONE documented fp32 operation order.

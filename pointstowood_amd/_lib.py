@@ -58,6 +58,7 @@ BN_GROUP = 16                                                                   
 BN_CHAIN_MAX, BN_CHAIN_ROWS = 3, 32                                                                # P2W_BN_CHAIN_*
 FEED_CHUNK, FEED_STREAM = 256, 0x50325746                                                          # P2W_FEED_*
 SAMPLE_STREAM, SAMPLE_TILE, SAMPLE_N_MAX = 0x50325753, 1024, 1 << 24                               # P2W_SAMPLE_*
+CAP_STREAM, CAP_N_MAX, CAP_S_MAX, CAP_OUT_MAX = 0x50325743, 1 << 30, 1 << 20, 1 << 38                  # P2W_CAP_*
 OPTIM_CHUNK, OPTIM_GROUP, OPTIM_MAX_TENSORS = 4096, 32, 4096                                       # P2W_OPTIM_*
 F32, F16, BF16 = 0, 1, 2                                                                           # P2W_F32, P2W_F16, P2W_BF16
 
@@ -114,6 +115,9 @@ SIGNATURES = {
                               _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "p2w_random_subset_ws_size": (_sz, [C.c_int64]),
     "p2w_random_subset": (_i32, [C.c_int64, C.c_int64, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "p2w_cap_subset_ws_size": (_sz, [C.c_int64, C.c_int64]),
+    "p2w_cap_subset": (_i32, [C.c_int64, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp,
+                              _sz, _vp]),
     "p2w_clip_adamw_ws_size": (_sz, [_vp, _i32]),
     "p2w_clip_adamw": (_i32, [C.POINTER(OptimTensor), _i32, C.POINTER(OptimHyper), _vp, _vp, _sz, _vp]),
     "p2w_tile_bbox": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),

@@ -1359,3 +1359,51 @@ def random_subset(n, k, seed, counter=(0, 0), device="cuda", keys=None, return_k
         elif return_keys and n > 0:                              # k = 0 launches nothing: the keys come from a draw of one row
             keys_out = random_subset(n, 1, seed, (c1, c2), device, keys, True)[1]
     return (idx, keys_out) if return_keys else idx
+
+
+def cap_subset(n, seg_start, seg_count, k, seed, counter=(0, 0), weight=None, row_id=None, keys=None, return_keys=False):
+    """``k`` rows of every one of ``S`` segments of a row space of ``n`` rows in one call, as an int64 ``[S, k]`` device tensor of
+    positions (``p2w_cap_subset``, ``csrc/p2w_sample.hip``): the voxeliser's cap.  ``seg_start``, ``seg_count``: int64 ``[S]`` device
+    tensors, disjoint segments in ascending order.
+
+    With ``weight`` (float32 ``[n]``) a segment keeps the ``k`` rows smallest in ``(key, position)``, ascending by position, ``key =
+    float32(-log(u) / weight)`` with ``u`` from word 0 of Philox4x32-10 at counter ``(row_id, counter[0], counter[1], P2W_CAP_STREAM)``
+    under ``seed`` - the law of ``torch.multinomial(weight, k)`` without replacement; a row whose weight is not finite and positive is
+    taken only when the others run out; a segment of at most ``k`` rows gives all of them, then ``-1``.  ``row_id`` (int64 ``[n]``;
+    default: the position) is what the generator knows a row by, so a segment's sample depends on its own ``(row_id, weight)`` pairs
+    alone.  ``keys`` (int32 ``[n]`` holding the 32-bit patterns) replaces generator and weights; ``return_keys`` also returns the key of
+    every row of every segment (int32 ``[n]``, other rows unwritten).
+
+    Without ``weight`` and ``keys``: ``k`` uniform draws with replacement per segment, in draw order.
+
+    ``n``, ``k``, ``seed`` and the counter words are Python integers; the call is enqueued on the current stream and waits for nothing."""
+    n, k, seed, c1, c2 = int(n), int(k), int(seed), int(counter[0]), int(counter[1])
+    _lib.require_cuda(seg_start, seg_count, weight, row_id, keys)
+    device, S = seg_start.device, seg_start.numel()
+    if seg_start.dtype != torch.int64 or seg_count.dtype != torch.int64 or seg_start.dim() != 1 or seg_count.shape != seg_start.shape:
+        raise ValueError("cap_subset: seg_start and seg_count must be int64 vectors of one length")
+    if not (0 <= n <= _lib.CAP_N_MAX and S <= _lib.CAP_S_MAX and 1 <= k <= _lib.CAP_N_MAX and S * k <= _lib.CAP_OUT_MAX):
+        raise ValueError(f"cap_subset: need 0 <= n <= {_lib.CAP_N_MAX}, S <= {_lib.CAP_S_MAX}, 1 <= k <= {_lib.CAP_N_MAX} and "
+                         f"S k <= {_lib.CAP_OUT_MAX}, got n = {n}, S = {S}, k = {k}")
+    for name, t, dtype in (("weight", weight, torch.float32), ("row_id", row_id, torch.int64), ("keys", keys, torch.int32)):
+        if t is not None and (t.dtype != dtype or t.shape != (n,)):
+            raise ValueError(f"cap_subset: {name} must be a {dtype} tensor of n elements")
+    select = weight is not None or keys is not None
+    if return_keys and not select:
+        raise ValueError("cap_subset: there are no keys without weight or keys (replacement mode)")
+    cont = lambda t: None if t is None else t.contiguous()
+    seg_start, seg_count, weight, row_id, keys = cont(seg_start), cont(seg_count), cont(weight), cont(row_id), cont(keys)
+    with torch.cuda.device(device):
+        idx = torch.empty((S, k), dtype=torch.int64, device=device)
+        keys_out = torch.empty(n, dtype=torch.int32, device=device) if return_keys else None
+        if S > 0:
+            ws = None
+            if select:
+                need = int(lib().p2w_cap_subset_ws_size(n, S))
+                if need == 0:
+                    raise RuntimeError(f"p2w_cap_subset_ws_size({n}, {S}) failed")
+                ws = torch.empty(need, dtype=torch.uint8, device=device)
+            check(lib().p2w_cap_subset(n, ptr(seg_start), ptr(seg_count), S, k, ptr(weight), ptr(row_id), seed & 0xffffffffffffffff,
+                                       c1 & 0xffffffff, c2 & 0xffffffff, ptr(keys), ptr(idx), ptr(keys_out), ptr(ws),
+                                       0 if ws is None else ws.numel(), stream()), "p2w_cap_subset")
+    return (idx, keys_out) if return_keys else idx

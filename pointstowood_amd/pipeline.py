@@ -53,7 +53,7 @@ def default_budget(total_points: int, world: int, free, dist=None, device=None) 
 
 def segment_plot(pc, model, grid_sizes=(2.0, 4.0), min_pts: int = 128, max_pts: int = 16384, is_wood: float = 0.5,
                  any_wood: float = 1.0, max_points: int | None = None, mode: str = "compat", generator=None, stats=None,
-                 dist=None, max_voxels: int | None = None, ground: bool = True, shard: str = "spatial", halo: float = 1.0):
+                 dist=None, max_voxels: int | None = None, ground: bool = True, shard: str = "spatial", halo: float = 1.0, cap=None):
     """pc: [N, >= 4] float tensor on the GPU (x, y, z, reflectance, ...), plot-local coordinates (fp32-safe).
     Returns (n_z [N], label [N], pwood [N]) float32 on the device: the three columns the reference appends
     (``predicter.py:233``).  ``stats`` (dict, optional) receives stage timings and counts.  ``max_points`` /
@@ -71,11 +71,15 @@ def segment_plot(pc, model, grid_sizes=(2.0, 4.0), min_pts: int = 128, max_pts: 
     the slab's covered range is repeated against a 4 x wider set, at most against everything - no further exchange); the
     per-point results are all-gathered once.  ``shard="slices"``: round 5's flow (all classified points to every rank, plot
     slices in input order).  Both give the single-process result bit for bit; with the default budget one all-reduce of a
-    scalar (the ranks' least free memory) precedes them."""
+    scalar (the ranks' least free memory) precedes them.
+
+    ``cap`` (``preprocessing.DeviceCap``, in place of ``generator``): the ``max_pts`` cap is drawn on the GPU as a function of the
+    cap's seed and counter and of each voxel's own points, so the ranks need no equal generator states - an equal ``cap`` is enough,
+    whatever any of them drew before."""
     dev = pc.device
     t0 = time.perf_counter()
     cells = []
-    vox, n_z = voxelise(pc, tuple(grid_sizes), min_pts, max_pts, mode=mode, generator=generator, ground=ground, cells=cells)
+    vox, n_z = voxelise(pc, tuple(grid_sizes), min_pts, max_pts, mode=mode, generator=generator, ground=ground, cells=cells, cap=cap)
     if stats is not None:
         _sync(dev)
         stats["voxelise_s"], t0 = time.perf_counter() - t0, time.perf_counter()

@@ -7,7 +7,9 @@ ids per grid size, voxels are contiguous segments of the sorted order.
 * ``ground_normalise``   - height above the per-5 m-XY-cell minimum z (``gpu_ground`` :37-53) -> ``n_z`` column.
 * ``quantile_normalize_reflectance`` - rank -> normal quantile -> [-1, 1] (:18-30).
 * ``voxelise``           - multi-resolution grid (:55-64), ``min_pts`` filter, cap at ``max_pts`` by reflectance-weighted
-                           sampling without replacement / uniform sampling WITH replacement (:116-120, as the reference).
+                           sampling without replacement / uniform sampling WITH replacement (:116-120, as the reference):
+                           per voxel from a ``torch.Generator``, or with ``cap=DeviceCap(seed)`` for all oversized voxels of a
+                           grid size in one ``p2w_cap_subset`` call.
   ``mode="compat"`` bins over every column like the reference (PyG ``voxel_grid`` is handed x, y, z, reflectance,
   ..., n_z - so voxels are also split by height above ground); ``mode="xyz"`` bins over x, y, z only.
 
@@ -103,8 +105,33 @@ class HipBackend:
 backend = HipBackend   # (tests of the host-side logic on the CPU put oracle.preprocess.TensorBackend here)
 
 
+class DeviceCap:
+    """``voxelise(..., cap=DeviceCap(seed))``: the ``max_pts`` cap of all oversized voxels of a grid size in one ``ops.cap_subset``
+    call (``p2w_cap_subset``) in place of one ``torch.multinomial`` / ``torch.randint`` per voxel.  The reference's laws (weighted
+    without replacement with reflectance, uniform with replacement without) from the package's counter-based generator: a voxel's
+    sample is a function of ``(seed, counter, index of the grid size)`` and the voxel's own (original point index, weight) pairs -
+    not of the other voxels, their order, or any generator's history.  Which points a seeded run keeps differs from the host draw's."""
+
+    def __init__(self, seed, counter=0):
+        self.seed, self.counter = int(seed), int(counter)
+
+
+def _device_cap(cap, grid_index, gathered, order, weight, starts, counts, max_pts):
+    """{voxel number: its ``[max_pts, cols]`` sample, a view} over the voxels with more than ``max_pts`` points; ``starts``, ``counts``:
+    the host's lists.  One small upload (the oversized runs), one operator call, one gather."""
+    from . import ops
+    over = [j for j, c in enumerate(counts) if c > max_pts]
+    if not over:
+        return {}
+    seg = torch.tensor([[starts[j] for j in over], [counts[j] for j in over]], dtype=torch.int64).to(gathered.device)
+    chosen = ops.cap_subset(gathered.shape[0], seg[0], seg[1], max_pts, cap.seed, counter=(grid_index, cap.counter),
+                            weight=None if weight is None else weight[order], row_id=order)
+    rows = gathered[chosen.reshape(-1)].view(len(over), max_pts, gathered.shape[1])
+    return {j: rows[i] for i, j in enumerate(over)}
+
+
 def voxelise(pc, grid_sizes=(2.0, 4.0), min_pts: int = 128, max_pts: int = 16384, mode: str = "compat", generator=None,
-             ground: bool = True, cells: list | None = None):
+             ground: bool = True, cells: list | None = None, cap: DeviceCap | None = None):
     """pc: [N, >=4] (x, y, z, reflectance, ...).  Returns (voxels, n_z): ``voxels`` is a list of ``[n, cols+1]`` float32
     tensors on ``pc.device`` in the reference's order (grid size major, ascending cell id).
 
@@ -115,16 +142,21 @@ def voxelise(pc, grid_sizes=(2.0, 4.0), min_pts: int = 128, max_pts: int = 16384
     ``cells`` (a list, optional) receives one ``(box_lo [v, 3], box_hi [v, 3])`` pair per grid size: the xyz cell of every
     voxel of that grid (all of a voxel's points share it: the grid's own arithmetic - column minimum, fp32 subtract / divide /
     truncate - on the voxel's first row, widened by a thousandth of the cell size) - what the spatially sharded
-    back-projection selects voxels by."""
+    back-projection selects voxels by.
+
+    ``cap`` (a ``DeviceCap``, optional; not together with ``generator``): voxels above ``max_pts`` are cut down on the GPU, one
+    operator call per grid size, see ``DeviceCap``.  With reflectance a capped voxel keeps its rows in the order of the uncapped voxel."""
     if mode not in ("compat", "xyz"):
         raise ValueError("mode must be 'compat' or 'xyz'")
+    if cap is not None and generator is not None:
+        raise ValueError("voxelise: cap draws from its own seed and counter; pass either cap or generator")
     pos = ground_normalise(pc.to(torch.float32)) if ground else pc.to(torch.float32).clone()
     refl_on = not bool(torch.all(pos[:, 3] == 0))
     if refl_on:
         pos[:, 3] = quantile_normalize_reflectance(pos[:, 3].reshape(-1))
     weight = (pos[:, 3] - pos[:, 3].min() + 1e-8) if refl_on else None
     voxels = []
-    for size in grid_sizes:
+    for grid_index, size in enumerate(grid_sizes):
         order, starts, counts = backend.grid_segments(pos if mode == "compat" else pos[:, :3], size, min_pts)
         # One gather puts every voxel's rows next to each other; a voxel that needs neither the max_pts sampling nor
         # the NaN-row filter (almost all of them) is then just a VIEW of that tensor: no per-voxel kernels, one sync.
@@ -142,9 +174,14 @@ def voxelise(pc, grid_sizes=(2.0, 4.0), min_pts: int = 128, max_pts: int = 16384
             first = gathered[starts, :3]          # (a kept run never starts with a non-finite row: those share the key that sorts last)
             c = ((first - lo3) / float(size)).to(torch.int64).to(torch.float32)
             cells.append((lo3 + c * float(size) - 1e-3 * float(size), lo3 + (c + 1.0) * float(size) + 1e-3 * float(size)))
-        for s, c, bad in zip(starts.tolist(), counts.tolist(), nan_cnt.tolist()):
+        starts, counts = starts.tolist(), counts.tolist()
+        capped = {} if cap is None else _device_cap(cap, grid_index, gathered, order, weight, starts, counts, max_pts)
+        for j, (s, c, bad) in enumerate(zip(starts, counts, nan_cnt.tolist())):
             if c <= max_pts and bad == 0:
                 voxels.append(gathered[s:s + c])
+                continue
+            if j in capped:
+                voxels.append(capped[j] if bad == 0 else capped[j][~torch.isnan(capped[j]).any(dim=1)])
                 continue
             idx = order[s:s + c]
             if c > max_pts:

@@ -45,6 +45,9 @@ def build_parser():
                         'fp16 / bf16 are the arithmetic of the reference autocast GPU path (about 1.7x faster, 1e-3..1e-2 off)')
     p.add_argument('--reference-sampler', action='store_true',
                    help='reproduce the reference BalancedBatchSampler exactly (drops the remainder, unseeded shuffles)')
+    p.add_argument('--cap_seed', type=int, default=None,
+                   help='Cut voxels above --max_pts down on the GPU, all of a grid size in one operator call, seeded with this value: '
+                        "the reference's laws from another random stream, so other points are kept than without it")
     return p
 
 
@@ -87,11 +90,13 @@ def segment_file(path, args):
     if rank == 0:
         print(f'Voxelising to {args.grid_size} grid sizes')
     stats = {}
-    gen = torch.Generator(device=device).manual_seed(0) if world > 1 else None   # identical max_pts sampling on every rank
+    from pointstowood_amd.preprocessing import DeviceCap
+    cap = None if args.cap_seed is None else DeviceCap(args.cap_seed)            # (the same sample on every rank by construction)
+    gen = torch.Generator(device=device).manual_seed(0) if world > 1 and cap is None else None   # identical max_pts sampling on every rank
     # input that already carries n_z (e.g. an *_ours.ply fed back in): the reference skips the height normalisation and
     # takes the LAST column for n_z (preprocessing.py:81-86,127)
     n_z, label, pwood = segment_plot(pc, model, args.grid_size, args.min_pts, args.max_pts, args.is_wood, args.any_wood,
-                                     stats=stats, generator=gen, dist=dist, ground='n_z' not in names)
+                                     stats=stats, generator=gen, dist=dist, ground='n_z' not in names, cap=cap)
     opath = os.path.join(os.path.dirname(path), os.path.splitext(os.path.basename(path))[0] + '_ours.ply')
     if rank != 0:
         return opath

@@ -86,6 +86,7 @@ int main() {
         }
         for (int N : {1, 64, 65, 256}) check("rowdot_carve", n, N, 0, [&](P2wArena& a) { rowdot_carve(a, i, N); });
         for (int B : {0, 1, 3, 257}) check("fd_carve", n, B, 0, [&](P2wArena& a) { fd_carve(a, n, B); });
+        for (long long S : {0ll, 1ll, 300ll, 4095ll, 4096ll}) check("cp_carve", n, S, 0, [&](P2wArena& a) { cp_carve(a, n, S); });
         for (int s : {1, 3, 7})
             for (int c : {2, 3, 8}) check("ev_carve", n, s, c, [&](P2wArena& a) { ev_carve(a, n, s, c); });
         for (int rows : {0, 1, 2, 257}) {

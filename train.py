@@ -50,6 +50,9 @@ def build_parser():
     p.add_argument('--device_sample', action='store_true',
                    help="Draw each level's training sample on the GPU: the reference's law (a uniform half of the rows) from another "
                         "random stream, a function of (seed, epoch, step, level), so a seeded run samples other points than without it")
+    p.add_argument('--device_cap', action='store_true',
+                   help="With --preprocess: cut voxels above --max_pts down on the GPU, all of a grid size in one operator call, "
+                        "seeded with --seed: the reference's laws from another random stream, so other points are kept than without it")
     p.add_argument('--amp', choices=['fp16', 'bf16'], default='fp16',
                    help="autocast dtype: fp16 with GradScaler(512) (the reference's loop), or bf16 without a loss scale, where a step "
                         "whose gradient norm is not finite is skipped and counted")
@@ -92,16 +95,18 @@ def preprocess(files, out_dir, args):
     """Every PLY of ``files`` through the voxeliser into ``out_dir/voxel_<i>.pt`` (float32 [n, >= 5] CPU tensors)."""
     import torch
     from pointstowood_amd import io as pio
-    from pointstowood_amd.preprocessing import voxelise
+    from pointstowood_amd.preprocessing import DeviceCap, voxelise
     if os.path.exists(out_dir):
         shutil.rmtree(out_dir)
     os.makedirs(out_dir, exist_ok=True)
     count = 0
-    for path in files:
+    for number, path in enumerate(files):
         names, arr, had = training_columns(pio.read_ply(path))
         print('Reflectance detected' if had else 'No reflectance detected, column added with zeros.')
         print(f'Voxelising {path} to {args.grid_size} grid sizes')
-        voxels, _ = voxelise(torch.from_numpy(arr).to('cuda'), args.grid_size, args.min_pts, args.max_pts, ground='n_z' not in names)
+        cap = DeviceCap(args.seed, counter=number) if getattr(args, 'device_cap', False) else None   # (a counter per file)
+        voxels, _ = voxelise(torch.from_numpy(arr).to('cuda'), args.grid_size, args.min_pts, args.max_pts, ground='n_z' not in names,
+                             cap=cap)
         for v in voxels:
             torch.save(v.cpu().clone(), os.path.join(out_dir, f'voxel_{count}.pt'))
             count += 1
