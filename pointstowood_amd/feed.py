@@ -248,8 +248,17 @@ class TrainingFeed:
         out.num_graphs = B
         return out
 
-    def __iter__(self):
+    def iterate(self, start: int = 0):
+        """The epoch's batches from batch ``start`` on (``0 <= start <= len(self)``; ``len(self)`` yields nothing): what a full
+        iteration yields behind its first ``start`` batches, bit for bit, without building those - a batch is a function of the epoch's
+        order and plan alone.  This is how a resumed run re-enters an epoch."""
+        start = int(start)
+        if not 0 <= start <= len(self):
+            raise ValueError(f"start must lie in [0, {len(self)}], got {start}")
         epoch = self.epoch
         plan = plan_to_device(self.plan(), self.set.device)
-        for ids in self.batches():
+        for ids in self.batches()[start:]:
             yield self.batch(ids, plan, epoch)
+
+    def __iter__(self):
+        return self.iterate(0)

@@ -188,6 +188,32 @@ class EpochScores:
                 self._loss[i] = loss.detach().reshape(()).to(torch.float32)
         self._batches += 1
 
+    def state(self):
+        """What has been added so far, for a training state: the first ``len(self)`` rows of the counts ([B, 5] int64) and of the
+        losses ([B] float32) as CPU tensors, the batch count, the threshold and the capacity.  One device-to-host copy each."""
+        B = self._batches
+        if self._counts is None:
+            counts, losses = torch.zeros((0, 5), dtype=torch.int64), torch.zeros(0, dtype=torch.float32)
+        else:
+            counts, losses = self._counts[:B].cpu(), self._loss[:B].cpu()
+        return {"counts": counts, "losses": losses, "batches": B, "threshold": self.threshold, "capacity": self._capacity}
+
+    @classmethod
+    def from_state(cls, state, device):
+        """The object that ``state()`` described, its buffers on ``device``: the remaining ``add`` calls on it give ``result()`` the
+        bits of the object that was never stored, ``matrices`` and ``losses`` included."""
+        B = int(state["batches"])
+        counts, losses = state["counts"], state["losses"]
+        if tuple(counts.shape) != (B, 5) or tuple(losses.shape) != (B,) or counts.dtype != torch.int64 or losses.dtype != torch.float32:
+            raise ValueError(f"a scores state of {B} batches needs int64 counts [{B}, 5] and float32 losses [{B}]")
+        self = cls(threshold=state["threshold"], capacity=max(int(state["capacity"]), B))
+        if B:
+            self._slot(torch.device(device))
+            self._counts[:B] = counts.to(device)
+            self._loss[:B] = losses.to(device)
+            self._batches = B
+        return self
+
     def result(self):
         from .evaluate import _raise_invalid, binary_metrics
         B = self._batches

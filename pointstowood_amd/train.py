@@ -124,6 +124,13 @@ class DeviceSampler:
     def draw(self, level, n, device):
         return ops.random_subset(n, n // 2, self.seed, counter=(4 * self.step + level, self.epoch), device=device)
 
+    def state_dict(self):
+        """Everything a draw depends on: three integers."""
+        return {"seed": self.seed, "epoch": self.epoch, "step": self.step}
+
+    def load_state_dict(self, state):
+        self.seed, self.epoch, self.step = int(state["seed"]), int(state["epoch"]), int(state["step"])
+
 
 class SAModule(torch.nn.Module):
     """The reference's set-abstraction level (``model.py:87-127``): sample centres, search their neighbours, ``PointNetConv`` on

@@ -21,11 +21,19 @@ the norm that ``clip_grad_norm_`` returns is read once per step and a step whose
 ``args.fused_step`` (``train.py --fused_step``, off when absent) replaces ``finish_step`` and both optimisers by ``optim.ClipAdamW``:
 unscale, clip, AdamW and the loss-scale law as one fused operator that decides skip-or-apply on the device (loss scale 512 under
 ``"fp16"``, none under ``"bf16"``).  The step then reads nothing back in either mode; the skipped count comes with the epoch's scores.
+
+``args.state_every``, ``args.stop_at`` and ``args.resume`` (``train.py --state_every / --stop_at / --resume``, all absent: the loop
+above) stop a run after any step and continue it with the bits of the run that never stopped: ``save_state`` / ``load_state`` /
+``restore_state`` carry everything that moves (DESIGN.md lists it), ``request_stop`` and ``stop_handlers`` end a run behind the step in
+flight, ``fingerprint_mismatch`` refuses a resume that could not be exact.
 """
 from __future__ import annotations
 
+import contextlib
+import hashlib
 import math
 import os
+import signal
 from collections import OrderedDict
 
 import numpy as np
@@ -69,6 +77,13 @@ class CosineAnnealingWarmupRestarts:
         lr = self.rate()
         for group in self.optimizer.param_groups:
             group["lr"] = lr
+
+    def state_dict(self):
+        """What moves: the cycle, its length and the step inside it.  The rate of the groups travels with the optimiser's state."""
+        return {"cycle": self.cycle, "cycle_steps": self.cycle_steps, "t": self.t}
+
+    def load_state_dict(self, state):
+        self.cycle, self.cycle_steps, self.t = int(state["cycle"]), int(state["cycle_steps"]), int(state["t"])
 
 
 def load_checkpoint(model, path, device):
@@ -121,6 +136,138 @@ def set_fused_bn_max(model, on=True):
     return n
 
 
+# ---- the training state: everything that moves during a run, so that a run can stop after any step and go on in another process ----
+
+STATE_FORMAT = 1
+BEST_KEYS = ("best_ba_train", "best_f1_train", "best_ba_test", "best_f1_test", "best_precision_test")
+_ABSENT = "<absent>"
+_stop_requested = False
+
+
+def request_stop():
+    """Asks the loop to stop: after the step in flight it writes the state and returns, as for ``--stop_at`` at that position."""
+    global _stop_requested
+    _stop_requested = True
+
+
+def stop_requested():
+    return _stop_requested
+
+
+def clear_stop():
+    global _stop_requested
+    _stop_requested = False
+
+
+@contextlib.contextmanager
+def stop_handlers():
+    """While open, SIGTERM and SIGINT call ``request_stop()`` - a job scheduler's signal then ends the run cleanly behind the step in
+    flight; on exit the previous handlers are back.  (Signal handlers belong to the main thread.)"""
+    def handler(signum, frame):
+        request_stop()
+    previous = {s: signal.signal(s, handler) for s in (signal.SIGTERM, signal.SIGINT)}
+    try:
+        yield
+    finally:
+        for s, h in previous.items():
+            signal.signal(s, h)
+
+
+def set_fingerprint(tset):
+    """(voxel count, SHA-256 of the ``lengths`` array) of a ``TrainingSet``: what a state remembers of a data set."""
+    return len(tset), hashlib.sha256(np.ascontiguousarray(tset.lengths, dtype=np.int64).tobytes()).hexdigest()
+
+
+def fingerprint(args, train_set, test_set=None):
+    """What a resumed run must share with the run that wrote the state for its bits to be the uninterrupted run's: a flat dict."""
+    fp = {"format": STATE_FORMAT, "seed": int(getattr(args, "seed", 141190)), "batch_size": int(args.batch_size),
+          "C": int(getattr(args, "C", 32)), "amp": str(getattr(args, "amp", "fp16")), "tune": bool(args.tune),
+          "num_epochs": int(args.num_epochs), "augmentation": bool(args.augmentation), "test": bool(args.test),
+          "fused_step": bool(getattr(args, "fused_step", False)), "device_sample": bool(getattr(args, "device_sample", False)),
+          "fused_bn_max": bool(getattr(args, "fused_bn_max", False))}
+    fp["train_voxels"], fp["train_lengths_sha256"] = set_fingerprint(train_set)
+    if test_set is not None:
+        fp["test_voxels"], fp["test_lengths_sha256"] = set_fingerprint(test_set)
+    return fp
+
+
+def fingerprint_mismatch(saved, current):
+    """-> [(field, saved value, current value)] of every field in which the two fingerprints differ, in sorted field order; a field
+    that one of them lacks counts as differing, its value there given as ``"<absent>"``.  Empty: the resume can be exact."""
+    out = []
+    for k in sorted(set(saved) | set(current)):
+        a, b = saved.get(k, _ABSENT), current.get(k, _ABSENT)
+        if type(a) is not type(b) or a != b:
+            out.append((k, a, b))
+    return out
+
+
+def save_state(path, *, epoch, step, model, optimizer, scaler, scheduler, history, best, consec_decreases, skipped, scores, sampler,
+               fingerprint):
+    """The whole training state at the position (``epoch``, ``step`` finished steps of it) into ``path``: written to ``path + ".tmp"``
+    and moved into place, so a kill during the write leaves the previous state as it was.  Tensors, numbers, strings, lists and
+    dicts only - ``torch.load(weights_only=True)`` reads it.  ``history``: the rows so far ([epochs done, columns], stored as
+    float64); ``best``: the five thresholds (``BEST_KEYS``); ``skipped``: the open epoch's running count on the plain route,
+    ``skipped_before`` under ``fused_step``; ``scores``: the open epoch's ``EpochScores``; ``scaler`` and ``sampler`` may be None.
+    Reads the process-wide generators without advancing them; waits for the device."""
+    device = next(model.parameters()).device
+    state = {
+        "format": STATE_FORMAT,
+        "fingerprint": dict(fingerprint),
+        "epoch": int(epoch),
+        "step": int(step),
+        "model": model.state_dict(),
+        "optimizer": optimizer.state_dict(),
+        "scaler": {} if scaler is None else scaler.state_dict(),
+        "scheduler": scheduler.state_dict(),
+        "history": torch.from_numpy(np.array(history, dtype=np.float64, ndmin=2)),
+        "best": {k: float(best[k]) for k in BEST_KEYS},
+        "consec_decreases": int(consec_decreases),
+        "skipped": int(skipped),
+        "scores": scores.state(),
+        "sampler": None if sampler is None else sampler.state_dict(),
+        "rng": {"cpu": torch.get_rng_state(), "cuda": torch.cuda.get_rng_state(device)},
+    }
+    tmp = path + ".tmp"
+    torch.save(state, tmp)
+    os.replace(tmp, path)
+
+
+def load_state(path, device):
+    """The dict that ``save_state`` wrote, read with ``weights_only=True``: the model's tensors, the optimiser's moments and its
+    ``record`` on ``device``; what lives on the host during a run (AdamW's step counts, the scores, the history, the generator
+    states) stays there."""
+    state = torch.load(path, map_location="cpu", weights_only=True)
+    if state.get("format") != STATE_FORMAT:
+        raise ValueError(f"{path}: state format {state.get('format')!r}, this build reads format {STATE_FORMAT}")
+    for k, v in state["model"].items():
+        state["model"][k] = v.to(device)
+    opt = state["optimizer"]
+    for st in opt["state"].values():
+        for k, v in st.items():
+            if k != "step" and torch.is_tensor(v):
+                st[k] = v.to(device)
+    if "record" in opt:
+        opt["record"] = opt["record"].to(device)
+    return state
+
+
+def restore_state(state, *, model, optimizer, scaler, scheduler, sampler):
+    """Puts the pieces of a loaded state back into freshly built objects: the model, the optimiser BEFORE the scheduler (so the
+    group's ``lr`` and ``betas`` are the saved ones), the scaler (an empty dict - a disabled scaler, or ``fused_step`` - is passed
+    over), the sampler, and last of all the two generator states: nothing that draws from the CPU generator may run between this
+    call and the first step."""
+    model.load_state_dict(state["model"])
+    optimizer.load_state_dict(state["optimizer"])
+    if scaler is not None and state.get("scaler"):
+        scaler.load_state_dict(state["scaler"])
+    scheduler.load_state_dict(state["scheduler"])
+    if sampler is not None:
+        sampler.load_state_dict(state["sampler"])
+    torch.cuda.set_rng_state(state["rng"]["cuda"], next(model.parameters()).device)
+    torch.set_rng_state(state["rng"]["cpu"])
+
+
 def SemanticTraining(args):
     """``args``: the namespace of ``train.py`` - ``wdir``, ``model``, ``trfile`` / ``tefile`` (voxel directories), ``batch_size``,
     ``num_epochs``, ``checkpoints``, ``augmentation``, ``test``, ``tune``, ``stop_early``, ``wandb``, ``seed``, ``device_sample`` (absent
@@ -130,7 +277,16 @@ def SemanticTraining(args):
     GEMM as ``ops.relu_bn_max``, on the GEMM's float16 / bfloat16 output as it is - the same function as the three statements, other
     roundings, the same bits on every run, the same ``state_dict``; ``args.fused_step`` (``train.py --fused_step``; absent or False:
     nothing changes): the optimiser is ``optim.ClipAdamW`` with the same ``lr`` and ``weight_decay`` and the loop is
-    ``optimizer.scale(loss).backward(); optimizer.step()`` - same history layout, same checkpoints.  Returns the history array."""
+    ``optimizer.scale(loss).backward(); optimizer.step()`` - same history layout, same checkpoints.  Returns the history array.
+
+    The training state (all absent: nothing changes).  ``args.state_every`` (``train.py --state_every N``): ``save_state`` into
+    ``model/<stem>_state.pth`` at the end of every epoch and, for N > 0, behind every N-th step of an epoch.  ``args.stop_at = (E, S)``
+    (``--stop_at E:S``): once S steps of epoch E are done the state is written and the history so far returned (S = the steps of an
+    epoch: behind that epoch's held-out pass and end-of-epoch work, as (E + 1, 0)); ``request_stop()`` does the same at the position
+    the loop is at.  ``args.resume`` (``--resume``; implies ``state_every = 0``): where the state file exists the run goes on from it -
+    the model file is neither loaded nor rewritten - and produces the bits of the run that was never stopped; a state whose
+    fingerprint differs from this run's raises ``ValueError`` before anything is written; where it does not exist the run starts as
+    usual."""
     if not torch.cuda.is_available():
         raise RuntimeError("SemanticTraining needs an MI355X (cuda) device; there is no CPU fallback")
     device = torch.device("cuda")
@@ -185,10 +341,38 @@ def SemanticTraining(args):
                                                            anneal_strategy="cos", div_factor=100)
 
     model_dir = os.path.join(args.wdir, "model")
-    os.makedirs(model_dir, exist_ok=True)
     model_path = os.path.join(model_dir, args.model)
     stem = os.path.splitext(args.model)[0]
-    if os.path.isfile(model_path):
+    steps = len(train_feed)
+
+    # the training state (all opt-in: with none of the three arguments nothing below saves, stops or reads a state)
+    state_path = os.path.join(model_dir, stem + "_state.pth")
+    state_every = getattr(args, "state_every", None)
+    stop_at = getattr(args, "stop_at", None)
+    resume = bool(getattr(args, "resume", False))
+    if resume and state_every is None:
+        state_every = 0
+    if state_every is not None and int(state_every) < 0:
+        raise ValueError(f"state_every must be at least 0, got {state_every}")
+    if stop_at is not None:
+        stop_at = (int(stop_at[0]), int(stop_at[1]))
+        if stop_at[0] < 1 or not 0 <= stop_at[1] <= steps:
+            raise ValueError(f"stop_at = (epoch >= 1, 0 <= step <= {steps} steps of an epoch), got {stop_at}")
+        if stop_at[1] == steps:                                 # behind an epoch's last step: behind its end-of-epoch work
+            stop_at = (stop_at[0] + 1, 0)
+    run_fingerprint = fingerprint(args, train_feed.set, None if test_feed is None else test_feed.set)
+    state = None
+    if resume and os.path.isfile(state_path):
+        state = load_state(state_path, device)
+        differing = fingerprint_mismatch(state["fingerprint"], run_fingerprint)
+        if differing:                                           # refused before anything is written
+            raise ValueError(f"{state_path} cannot be resumed exactly by this run; differing fields (saved state, this run): "
+                             + "; ".join(f"{k}: {a!r}, {b!r}" for k, a, b in differing))
+
+    os.makedirs(model_dir, exist_ok=True)
+    if state is not None:
+        print(f"Resuming at epoch {state['epoch']}, step {state['step']}")       # the state wins: the model file is not touched
+    elif os.path.isfile(model_path):
         print("Loading model")
         try:
             load_checkpoint(model, model_path, device)
@@ -211,17 +395,55 @@ def SemanticTraining(args):
     history = None
     consec_decreases = 0
     skipped_before = 0                                          # (fused_step) the device's count at the end of the last epoch
+    start_epoch, start_step = 1, 0
 
-    for epoch in range(1, args.num_epochs + 1):
+    def save(epoch, step, scores, skipped):
+        save_state(state_path, epoch=epoch, step=step, model=model, optimizer=optimizer, scaler=None if fused_step else scaler,
+                   scheduler=lr_scheduler, history=np.zeros((0, 11 if args.test else 7)) if history is None else history,
+                   best=dict(zip(BEST_KEYS, (best_ba_train, best_f1_train, best_ba_test, best_f1_test, best_precision_test))),
+                   consec_decreases=consec_decreases, skipped=skipped_before if fused_step else skipped, scores=scores,
+                   sampler=model.sampler, fingerprint=run_fingerprint)
+        print(f"Saved the training state at epoch {epoch}, step {step}")
+
+    def stops(epoch, step):
+        """Whether the run ends at this position: ``stop_at``, or a stop request (which is cleared)."""
+        if stop_requested():
+            clear_stop()
+            return True
+        return stop_at == (epoch, step)
+
+    if state is not None:
+        start_epoch, start_step = state["epoch"], state["step"]
+        history = state["history"].numpy() if state["history"].shape[0] else None
+        best_ba_train, best_f1_train, best_ba_test, best_f1_test, best_precision_test = (state["best"][k] for k in BEST_KEYS)
+        consec_decreases = state["consec_decreases"]
+        if fused_step:
+            skipped_before = state["skipped"]
+        restore_state(state, model=model, optimizer=optimizer, scaler=None if fused_step else scaler, scheduler=lr_scheduler,
+                      sampler=model.sampler)                    # ends with the generator states: nothing below draws before the step
+    if stops(start_epoch, start_step):                          # a resumed run's state file already holds this position
+        if state is None:
+            save(start_epoch, start_step, EpochScores(capacity=steps), 0)
+        return history
+
+    for epoch in range(start_epoch, args.num_epochs + 1):
         model.train()
         print("\n=============================================================================================")
         print("EPOCH ", epoch)
         train_feed.set_epoch(epoch)
         if model.sampler is not None:
             model.sampler.set_epoch(epoch)
-        scores = EpochScores(capacity=len(train_feed))
-        skipped = 0
-        for data in train_feed:
+        first = start_step if epoch == start_epoch else 0       # a resumed epoch goes on behind its finished steps
+        if first:
+            if model.sampler is not None:
+                model.sampler.step = first
+            scores = EpochScores.from_state(state["scores"], device)
+            skipped = 0 if fused_step else state["skipped"]
+        else:
+            scores = EpochScores(capacity=steps)
+            skipped = 0
+        step = first
+        for data in train_feed.iterate(first):
             optimizer.zero_grad()
             with torch.autocast("cuda", dtype=AMP_DTYPES[amp]):
                 outputs = model(data)
@@ -233,6 +455,13 @@ def SemanticTraining(args):
                 scaler.scale(loss).backward()
                 skipped += finish_step(model, optimizer, scaler, amp)
             scores.add(outputs, data.y, loss)
+            step += 1
+            if step < steps:                                    # (behind the last step the epoch's end comes first)
+                if stops(epoch, step):
+                    save(epoch, step, scores, skipped)
+                    return history
+                if state_every and step % state_every == 0:
+                    save(epoch, step, scores, skipped)
         lr_scheduler.step()
         tr = scores.result()                                    # the epoch's one device-to-host copy
         lr = optimizer.param_groups[0]["lr"]
@@ -270,6 +499,8 @@ def SemanticTraining(args):
             if consec_decreases >= 10:
                 print(f"\nStopping early at epoch {epoch} - training accuracy decreased for {consec_decreases} consecutive epochs")
                 print(f"Best accuracy was {max(history[:, 3]):.4f} at epoch {np.argmax(history[:, 3]) + 1}")
+                if state_every is not None:                     # the run is over: a resume of this state has nothing left to do
+                    save(args.num_epochs + 1, 0, EpochScores(capacity=steps), 0)
                 break
 
         base = os.path.basename(args.model)
@@ -291,4 +522,11 @@ def SemanticTraining(args):
                        "Recall": np.around(tr["recall"], 4), "F1": np.around(tr["f1"], 4),
                        "Test F1": np.around(te["f1"], 4) if te is not None else 0.0,
                        "Test Accuracy": np.around(te["balanced_accuracy"], 4) if te is not None else 0.0})
+
+        # the epoch is wholly finished: its state is the next epoch's position before its first step
+        stop = stops(epoch + 1, 0)
+        if state_every is not None or stop:
+            save(epoch + 1, 0, EpochScores(capacity=steps), 0)
+        if stop:
+            break
     return history

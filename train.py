@@ -14,6 +14,13 @@ centred and collated there (``pointstowood_amd.feed``).  ``--fused_bn_max`` (def
 ``ops.PointNetConv`` of the model: ReLU, training-mode BatchNorm and the segment max behind the layer-2 GEMM run as ``ops.relu_bn_max``,
 which under ``--amp`` of either dtype reads the GEMM's 16-bit output and writes its gradient in that dtype.  ``--fused_step`` (default
 off) runs unscale, clip, AdamW and the loss-scale law of every step as one fused operator (``pointstowood_amd.optim.ClipAdamW``).
+
+A run can be cut into pieces: ``--state_every N`` writes the whole training state to ``model/<model>_state.pth`` at every epoch's end
+(N > 0: and after every N-th step), ``--stop_at E:S`` writes it and exits once S steps of epoch E are done, and with either, or with
+``--resume``, SIGTERM and SIGINT do the same after the step in flight.  ``--resume`` continues from that file where it exists - the
+continued run produces the bits of the uninterrupted one - and starts as usual where it does not:
+
+    python train.py --wdir DIR ... --resume --state_every 200        # the same line for every submission of a time-boxed job
 """
 from __future__ import annotations
 
@@ -64,7 +71,38 @@ def build_parser():
                    help="Run unscale, clip_grad_norm_(1.0), AdamW and the loss-scale update of every step as one fused operator "
                         "(optim.ClipAdamW): skip-or-apply is decided on the GPU and no step reads the device; a documented fp32 "
                         "operation order, other roundings than torch's AdamW; the skipped count is printed with every epoch")
+    p.add_argument('--state_every', type=int, default=None, metavar='N',
+                   help="Write the whole training state (model, optimiser, loss scale, schedule, history, best-model thresholds, "
+                        "open epoch's scores, random generators) to model/<model>_state.pth at the end of every epoch and, for "
+                        "N > 0, after every N-th step of an epoch; each save waits for the GPU once")
+    p.add_argument('--stop_at', type=stop_position, default=None, metavar='E:S',
+                   help="Write the training state and exit (status 0) once S steps of epoch E are done; S = 0: before the first step "
+                        "of epoch E; S = the steps of an epoch: after that epoch's test pass and checkpoints")
+    p.add_argument('--resume', action='store_true', default=None,
+                   help="Continue from model/<model>_state.pth where it exists (else start as usual): the continued run produces "
+                        "the bits of the uninterrupted one; implies --state_every 0; the old checkpoints are kept; a state written "
+                        "with other flags, another seed, batch size, --num_epochs or data set is refused; not with --preprocess. "
+                        "With any of the three flags SIGTERM and SIGINT stop the run after the step in flight, state written")
     return p
+
+
+def stop_position(text):
+    """``E:S`` -> (E, S): epoch E >= 1, S >= 0 finished steps of it."""
+    try:
+        epoch, step = (int(v) for v in text.split(':'))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"E:S (two integers) is needed, got {text!r}") from None
+    if epoch < 1 or step < 0:
+        raise argparse.ArgumentTypeError(f"an epoch from 1 and a step from 0 are needed, got {text!r}")
+    return epoch, step
+
+
+def parse_args(argv=None):
+    p = build_parser()
+    args = p.parse_args(argv)
+    if args.resume and args.preprocess:
+        p.error("--resume continues a run on the voxels it was started on: it cannot be combined with --preprocess")
+    return args
 
 
 def training_columns(columns):
@@ -114,7 +152,7 @@ def preprocess(files, out_dir, args):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     import torch
     if args.device != 'cuda' or not torch.cuda.is_available():
         raise SystemExit('train.py needs an MI355X: the HIP path has no CPU fallback')
@@ -123,9 +161,11 @@ def main(argv=None):
     args.mode = 'train'
     print('Mode: {}'.format(args.mode))
 
-    # checkpointing, as the reference organises it (train.py:88-94): the old checkpoints are archived, then removed
+    # checkpointing, as the reference organises it (train.py:88-94): the old checkpoints are archived, then removed - unless this
+    # run continues the one that wrote them (--resume with its state file there)
     args.checkpoints = np.arange(0, args.num_epochs + 1, max(1, int(args.num_epochs / args.checkpoint_saves)))
-    old = glob.glob(os.path.join(args.wdir, 'checkpoints', '*.pth'))
+    resuming = bool(args.resume) and os.path.isfile(os.path.join(args.wdir, 'model', os.path.splitext(args.model)[0] + '_state.pth'))
+    old = [] if resuming else glob.glob(os.path.join(args.wdir, 'checkpoints', '*.pth'))
     if old:
         shutil.make_archive(os.path.join(args.wdir, 'checkpoints_backup'), 'zip', os.path.join(args.wdir, 'checkpoints'))
     for f in old:
@@ -142,8 +182,11 @@ def main(argv=None):
     if args.augmentation:
         print('Training with data augmentation performed on 25% of samples')
 
-    from pointstowood_amd.trainer import SemanticTraining
-    return SemanticTraining(args)
+    from pointstowood_amd.trainer import SemanticTraining, stop_handlers
+    if args.state_every is None and args.stop_at is None and not args.resume:
+        return SemanticTraining(args)
+    with stop_handlers():                                       # SIGTERM / SIGINT: the state is written behind the step in flight
+        return SemanticTraining(args)
 
 
 if __name__ == '__main__':
