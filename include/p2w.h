@@ -1035,6 +1035,9 @@ int32_t p2w_bn_relu_rowdot_bwd(const float* g, const float* z, int32_t ldz, cons
  *                         values is exact)
  *   tz  z and dz          (p2w_relu_bn_max_io / _bwd_io): P2W_F32, P2W_F16 or P2W_BF16; g and out stay fp32, like ext, arg and every
  *                         [C2] vector (an extremum of widened values is exact); both directions share p2w_relu_bn_max_ws_bytes
+ *   th  H1                (p2w_edge_l1_io): P2W_F32, P2W_F16 or P2W_BF16; P, Wg, rec_* and geo stay fp32
+ *   tg  gH                (p2w_edge_l1_bwd_io): P2W_F32, P2W_F16 or P2W_BF16; P, geo, Wg, gP, gR and gWg stay fp32, H1 is no argument
+ *                         (the ReLU mask is recomputed); the workspace is p2w_edge_l1_bwd_ws_bytes
  * The four chain entry points take P2W_BF16.  p2w_bn_relu_rowdot_io / _bwd_io and p2w_segment_max_arg_io / _bwd_io have one code
  * each and answer 2 with P2W_EUNSUPPORTED like any other unknown code (tests/test_gpu_half_io.py: test_refusals_launch_nothing
  * asserts it of them); their bfloat16 instantiations are the four p2w_*_bf16 entry points below the _io ones.
@@ -1078,6 +1081,25 @@ int32_t p2w_relu_bn_max_bwd_io(const float* g, const void* z, int32_t tz, int32_
                                const float* ext, const float* mean, const float* invstd, const float* gamma, int32_t E, int32_t M,
                                int32_t C2, void* dz, int32_t lddz, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
                                p2w_stream_t stream);
+/* Layer 1 of the edge MLP with H1 in fp32, float16 or bfloat16 (th), and its backward with gH in any of the three (tg).  The forward
+ * is p2w_edge_l1 (which calls it with P2W_F32): P, rec_*, Wg and geo stay fp32, the arithmetic and its order are the namesake's, a
+ * 16-bit H1 is the namesake's fp32 H1 rounded once.  C1 a multiple of 4: H1 needs 4 sizeof(element) bytes of alignment (8 for a
+ * 16-bit type) and ldh a multiple of 4 (P2W_EALIGN).
+ * The backward is NOT given H1.  A stored float16 zero may stand for an fp32 h in (0, 2^-25] (bfloat16: below 2^-134), so a mask
+ * read back from a 16-bit H1 would differ from the fp32 route's; the kernels recompute
+ *   h = relu((((P[j, c] + geo0 Wg[0, c]) + geo1 Wg[1, c]) + geo2 Wg[2, c]) + geo3 Wg[3, c]),  j = src[e],
+ * with the forward's own statements (no contraction: the same bits) from P[n_src, C1] (pitch ldp, fp32 - the forward's P), geo, src and
+ * Wg, and take gZ[e, c] = (h > 0) ? gH[e, c] : 0; an edge whose source is outside [0, n_src) has gZ = 0 (the forward wrote 0 there).
+ * Everything else is p2w_edge_l1_bwd: the sort, the run sums, the chunks, gR, the workspace (p2w_edge_l1_bwd_ws_bytes) and the fp32
+ * gP, gR, gWg - bit for bit what p2w_edge_l1_bwd gives on the widened gH and the fp32 H1.  C1 a multiple of 4: ldg, ldp, ldgp
+ * multiples of 4, gH aligned to 4 sizeof(element) bytes, P, Wg, gP, gWg to 16 (P2W_EALIGN); geo and ws always 16.
+ *   th  H1 (p2w_edge_l1_io), tg  gH (p2w_edge_l1_bwd_io): P2W_F32, P2W_F16 or P2W_BF16; any other code: P2W_EUNSUPPORTED, checked first */
+int32_t p2w_edge_l1_io(const float* P, int32_t ldp, const float* rec_src, const float* rec_dst, const int32_t* ptr, const int32_t* src,
+                       const float* Wg, int32_t n_src, int32_t M, int32_t E, int32_t C1, float* geo, void* H1, int32_t th, int32_t ldh,
+                       p2w_stream_t stream);
+int32_t p2w_edge_l1_bwd_io(const void* gH, int32_t tg, int32_t ldg, const float* P, int32_t ldp, const float* geo, const int32_t* src,
+                           const float* Wg, int32_t n_src, int32_t E, int32_t C1, float* gP, int32_t ldgp, float* gR, float* gWg,
+                           void* ws, size_t ws_bytes, p2w_stream_t stream);
 /* The head and the segment max on bfloat16 tensors: what their _io entry points would do for tz / tx = P2W_BF16 - the namesake's
  * arguments without the dtype code, z and dz (x and grad_x) bfloat16, everything else as above: the same launches, sums, workspace and
  * status codes, the widening load exact, every bfloat16 store one rounding to nearest even, 8-byte accesses where an 8-byte aligned

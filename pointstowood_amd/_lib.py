@@ -188,6 +188,8 @@ SIGNATURES = {
                                   _sz, _vp]),
     "p2w_relu_bn_max_bwd_io": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _sz,
                                       _vp]),
+    "p2w_edge_l1_io": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp]),
+    "p2w_edge_l1_bwd_io": (_i32, [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
     "p2w_bn_relu_rowdot_bf16": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _i32, _i32, _vp, _vp, _vp, _vp, _sz,
                                        _vp]),
     "p2w_bn_relu_rowdot_bwd_bf16": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -318,13 +318,13 @@ def knn_interpolate(x, pos_x, pos_y, batch_x=None, batch_y=None, k=3, num_worker
     return _interp_forward(x, rc, rf, nbr, deg, k)
 
 
-def _edge_l1_forward(P, Wg, rs, rd, csr, src):
-    """(geo [E, 4], H1 [E, C1]) of ``p2w_edge_l1``: fp32, contiguous inputs."""
+def _edge_l1_forward(P, Wg, rs, rd, csr, src, out_dtype=None):
+    """(geo [E, 4], H1 [E, C1]) of ``p2w_edge_l1_io``: fp32, contiguous inputs; H1 in ``out_dtype`` (None: fp32)."""
     (n_src, C1), M, E = P.shape, rd.shape[0], src.numel()
     geo = torch.empty((E, 4), dtype=torch.float32, device=P.device)
-    H1 = torch.empty((E, C1), dtype=torch.float32, device=P.device)
-    check(lib().p2w_edge_l1(ptr(P), C1, ptr(rs), ptr(rd), ptr(csr), ptr(src), ptr(Wg), n_src, M, E, C1, ptr(geo), ptr(H1), C1,
-                            stream()), "edge_layer1")
+    H1 = torch.empty((E, C1), dtype=out_dtype or torch.float32, device=P.device)
+    check(lib().p2w_edge_l1_io(ptr(P), C1, ptr(rs), ptr(rd), ptr(csr), ptr(src), ptr(Wg), n_src, M, E, C1, ptr(geo), ptr(H1), _code(H1), C1,
+                               stream()), "edge_layer1")
     return geo, H1
 
 
@@ -366,7 +366,42 @@ class _EdgeLayer1(torch.autograd.Function):
         return gP.to(ctx.dtypes[0]), gWg.to(ctx.dtypes[1]), gpos, None, None, None
 
 
-def edge_layer1(P, Wg, pos_src, pos_dst, edge_index):
+class _EdgeLayer1Half(torch.autograd.Function):
+    """``_EdgeLayer1`` with H1 in float16 or bfloat16 (``p2w_edge_l1_io`` / ``p2w_edge_l1_bwd_io``): no [E, C1] tensor is saved - the
+    backward recomputes the ReLU mask from the widened fp32 P, geo, src and Wg with the forward's own statements, so it is the fp32
+    H1's mask whatever the 16-bit store rounded to zero - and the gradient is read in the dtype it arrives in."""
+
+    @staticmethod
+    def forward(ctx, P, Wg, pos_src, rd, csr, src, out_dtype):
+        with _no_autocast():
+            Pc, Wc = _f32c(P), _f32c(Wg)
+            geo, H1 = _edge_l1_forward(Pc, Wc, _f32c(pos_src), rd, csr, src, out_dtype)
+            ctx.save_for_backward(Pc, geo, src, Wc)
+            ctx.dtypes = (P.dtype, Wg.dtype, pos_src.dtype)
+            ctx.mark_non_differentiable(geo)
+            return H1, geo
+
+    @staticmethod
+    def backward(ctx, grad_H1, _grad_geo):
+        with _no_autocast():
+            P, geo, src, Wg = ctx.saved_tensors
+            (n_src, C1), E, dev = P.shape, src.numel(), P.device
+            g = _lib.aligned16(grad_H1.detach().contiguous()) if grad_H1.dtype in _HALF_TYPES else _f32c(grad_H1)
+            gP = torch.empty((n_src, C1), dtype=torch.float32, device=dev)
+            gR = torch.empty(n_src, dtype=torch.float32, device=dev)
+            gWg = torch.empty((4, C1), dtype=torch.float32, device=dev)
+            ws = torch.empty(ws_bytes("edge_l1_bwd", E, n_src, C1), dtype=torch.uint8, device=dev)
+            check(lib().p2w_edge_l1_bwd_io(ptr(g), _code(g), C1, ptr(P), C1, ptr(geo), ptr(src), ptr(Wg), n_src, E, C1, ptr(gP), C1, ptr(gR),
+                                           ptr(gWg), ptr(ws), ws.numel(), stream()), "edge_layer1 backward")
+            gpos = None
+            if ctx.needs_input_grad[2]:
+                gpos = torch.zeros((n_src, 4), dtype=torch.float32, device=dev)
+                gpos[:, 3] = gR
+                gpos = gpos.to(ctx.dtypes[2])
+            return gP.to(ctx.dtypes[0]), gWg.to(ctx.dtypes[1]), gpos, None, None, None, None
+
+
+def edge_layer1(P, Wg, pos_src, pos_dst, edge_index, out_dtype=None):
     """Layer 1 of the reference's edge MLP (``pointnet.py:116-132`` followed by ``local_nn[0]``, ``model.py:198-202``), hoisted:
     ``H1[e] = relu(P[j] + geo[e] @ Wg)`` for edge e = (j -> i) with ``P = x_src @ W1[:, :F_in].T + b1`` ``[n_src, C1]`` computed by
     the caller once per source point, ``Wg`` ``[4, C1]`` = the transposed last four columns of ``W1`` and ``geo[e] = ((pos_j - pos_i)
@@ -375,10 +410,18 @@ def edge_layer1(P, Wg, pos_src, pos_dst, edge_index):
 
     Differentiable with respect to ``P``, ``Wg`` and ``pos_src[:, 3]`` (the other columns of ``pos_src`` get zeros, ``pos_dst``
     none: positions get no gradient anywhere in this module).  The backward uses no floating-point atomics: the same bits on
-    every run.  Computes in fp32 under autocast.  Without a gradient to track nothing is saved."""
+    every run.  Computes in fp32 under autocast.  Without a gradient to track nothing is saved.
+
+    ``out_dtype`` None (the default, whatever autocast says): H1 in fp32, and the fp32 H1 is saved for the backward as its ReLU
+    mask.  ``torch.float16`` / ``torch.bfloat16``: the kernel stores H1 in that dtype - the fp32 result rounded once, the bits of the
+    default call followed by ``.to(out_dtype)`` - no [E, C1] tensor is saved (the backward recomputes the mask from the fp32 P, geo
+    and Wg, bit for bit the fp32 H1's), and the output's gradient is read in the dtype it arrives in: the same gradients as the
+    default call followed by ``.to(out_dtype)``, bit for bit."""
     _lib.require_cuda(P, Wg, pos_src, pos_dst, edge_index)
     if P.dim() != 2 or tuple(Wg.shape) != (4, P.shape[1]) or pos_src.shape != (P.shape[0], 4) or pos_dst.dim() != 2 or pos_dst.shape[1] != 4:
         raise RuntimeError("edge_layer1: P [n_src, C1], Wg [4, C1], pos_src [n_src, 4], pos_dst [M, 4]")
+    if out_dtype is not None and out_dtype not in _HALF_TYPES:
+        raise RuntimeError("edge_layer1: out_dtype is None (fp32), torch.float16 or torch.bfloat16")
     j, i = edge_index[0].to(torch.int64), edge_index[1].to(torch.int64)
     n_src, M = P.shape[0], pos_dst.shape[0]
     if j.numel() and (bool((i[1:] < i[:-1]).any()) or int(i[0]) < 0 or int(i[-1]) >= M or int(j.min()) < 0 or int(j.max()) >= n_src):
@@ -386,8 +429,10 @@ def edge_layer1(P, Wg, pos_src, pos_dst, edge_index):
     csr = torch.searchsorted(i.contiguous(), torch.arange(M + 1, device=i.device, dtype=torch.int64)).to(torch.int32)
     src, rd = j.to(torch.int32).contiguous(), _f32c(pos_dst)
     if torch.is_grad_enabled() and (P.requires_grad or Wg.requires_grad or pos_src.requires_grad):
+        if out_dtype is not None:
+            return _EdgeLayer1Half.apply(P, Wg, pos_src, rd, csr, src, out_dtype)[0]
         return _EdgeLayer1.apply(P, Wg, pos_src, rd, csr, src)[0]
-    return _edge_l1_forward(_f32c(P), _f32c(Wg), _f32c(pos_src), rd, csr, src)[1]
+    return _edge_l1_forward(_f32c(P), _f32c(Wg), _f32c(pos_src), rd, csr, src, out_dtype)[1]
 
 
 def _relu_bn_max_forward(zc, gamma, beta, csr, M, bn):
@@ -629,7 +674,8 @@ class PointNetConv(MessagePassing):
         if lin1.weight.shape[1] != F_in + 4 or pos_src.shape[1] != 4 or pos_dst.shape[1] != 4:
             raise RuntimeError("PointNetConv: local_nn must take F_in + 4 inputs, pos must be [n, 4]")
         P = torch.nn.functional.linear(x_src, lin1.weight[:, :F_in], lin1.bias)     # hoisted layer 1, once per source point
-        H1 = edge_layer1(P, lin1.weight[:, F_in:F_in + 4].t(), pos_src, pos_dst, edge_index)
+        # (under autocast with half_io, H1 goes to local_nn[1][0] in the autocast dtype as the kernel stored it)
+        H1 = edge_layer1(P, lin1.weight[:, F_in:F_in + 4].t(), pos_src, pos_dst, edge_index, out_dtype=_gemm_dtype(P))
         if self.fused_bn_max:       # (edge_layer1 has checked that the targets ascend inside [0, M))
             out = _relu_bn_max_sorted(nn[1][0](H1), edge_index[1], nn[1][2], pos_dst.shape[0])
         else:
