@@ -227,10 +227,14 @@ def check(code: int, what: str = "") -> None:
 
 
 def ws_bytes(name: str, *args) -> int:
-    """Workspace size of entry point ``name`` (``p2w_<name>_ws_bytes``); 0 is the library's answer to sizes it refuses."""
-    need = int(getattr(lib(), f"p2w_{name}_ws_bytes")(*args))
+    """Workspace size of entry point ``name``: ``p2w_<name>_ws_bytes`` or, where the header calls the query that, ``p2w_<name>_ws_size``
+    (no entry point has both); 0 is the library's answer to sizes it refuses."""
+    symbol = f"p2w_{name}_ws_bytes"
+    if symbol not in SIGNATURES:
+        symbol = f"p2w_{name}_ws_size"
+    need = int(getattr(lib(), symbol)(*args))
     if need == 0:
-        raise RuntimeError(f"p2w_{name}_ws_bytes{args} failed")
+        raise RuntimeError(f"{symbol}({', '.join(map(str, args))}) failed")
     return need
 
 

@@ -63,8 +63,9 @@ def _xyzr(pos):
     return out
 
 
-def _ws(n, device):
-    return torch.empty(ws_bytes("voxel_sample", max(n, 1)), dtype=torch.uint8, device=device)
+def _ws(name, *args, device):
+    """The workspace of entry point ``name`` for these sizes (``_lib.ws_bytes``: a refused size is a RuntimeError)."""
+    return torch.empty(ws_bytes(name, *args), dtype=torch.uint8, device=device)
 
 
 def voxel_grid(pos, size, batch=None):
@@ -75,7 +76,7 @@ def voxel_grid(pos, size, batch=None):
     nb = _num_batches(batch)
     x = _xyzr(pos)
     cell = torch.empty(n, dtype=torch.int64, device=pos.device)
-    ws, csr = _ws(n, pos.device), _csr(batch, nb)
+    ws, csr = _ws("voxel_sample", max(n, 1), device=pos.device), _csr(batch, nb)
     check(lib().p2w_voxel_grid(ptr(x), ptr(csr), nb, n, float(size), ptr(cell), ptr(ws), ws.numel(), stream()),
           "voxel_grid")
     return cell
@@ -88,7 +89,7 @@ def consecutive_cluster(src):
     inv = torch.empty(n, dtype=torch.int32, device=src.device)
     perm = torch.empty(n, dtype=torch.int32, device=src.device)
     cnt = torch.zeros(1, dtype=torch.int32, device=src.device)
-    ws = _ws(n, src.device)
+    ws = _ws("voxel_sample", max(n, 1), device=src.device)
     check(lib().p2w_consecutive_cluster(ptr(src), n, ptr(inv), ptr(perm), ptr(cnt), ptr(ws), ws.numel(), stream()),
           "consecutive_cluster")
     return inv.to(torch.int64), perm[: int(cnt)].to(torch.int64)
@@ -178,6 +179,62 @@ def _no_autocast():
     return torch.autocast("cuda", enabled=False)
 
 
+def _entry(name, t):
+    """(entry point, its dtype arguments) of the head and the segment max for the big tensor ``t``: ``p2w_<name>_bf16`` has bfloat16 in its
+    name, ``p2w_<name>_io`` takes the code of fp32 or float16 (and refuses P2W_BF16)."""
+    if t.dtype == torch.bfloat16:
+        return getattr(lib(), f"p2w_{name}_bf16"), ()
+    return getattr(lib(), f"p2w_{name}_io"), (_code(t),)
+
+
+def _half_twin(base, doc):
+    """The ``half_io`` route of ``base`` as a class of its own, ``<base>Half`` (so ``grad_fn`` says which route ran): the same argument
+    list, ``base._forward(..., keeps_half=True)`` and ``base._backward`` with autocast off and without the fp32 route's cast of the inputs
+    - the big float16 / bfloat16 tensor goes to the kernels as it is, is the tensor saved, and gets its gradient in its dtype."""
+    def forward(ctx, *args):
+        with _no_autocast():
+            return base._forward(ctx, *args, keeps_half=True)
+
+    def backward(ctx, *grads):
+        with _no_autocast():
+            return base._backward(ctx, *grads)
+
+    return type(base.__name__ + "Half", (base,), {"forward": staticmethod(forward), "backward": staticmethod(backward), "__doc__": doc})
+
+
+# The prelude of the operators that own a training-mode BatchNorm1d (relu_bn_max, bn_chain, relu_bn, bn_relu_rowdot).  Each one refuses in
+# this order - _check_bn, its shapes, its out_dtype - takes its eval-mode shortcut, and only then _training_tick: a refused call and an
+# eval-mode call move no counter and no statistic.
+def _check_bn(bn, who, not_a_bn=None):
+    if not isinstance(bn, torch.nn.BatchNorm1d):
+        raise TypeError(not_a_bn or f"{who}: bn must be a torch.nn.BatchNorm1d")
+    if not bn.affine or not bn.track_running_stats or bn.momentum is None:
+        raise NotImplementedError(f"{who} supports BatchNorm1d(affine=True, track_running_stats=True, momentum=<float>) as the reference builds it")
+
+
+def _training_tick(z, bns):
+    """PyTorch's refusal of a batch of fewer than two rows, then ``num_batches_tracked`` of every ``bn`` as its forward would count."""
+    if z.shape[0] < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {z.size()}")
+    for bn in bns:
+        if bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
+
+
+def _running(bns):
+    """[(running_mean, running_var)] as the kernels update them in place: fp32 and contiguous - the modules' own storage wherever it is."""
+    return [tuple(t.detach().to(torch.float32).contiguous() for t in (bn.running_mean, bn.running_var)) for bn in bns]
+
+
+def _write_back(bns, running):
+    """After the launch: a pair that ``_running`` had to copy goes back into its module."""
+    with torch.no_grad():
+        for bn, pair in zip(bns, running):
+            for mine, theirs in zip(pair, (bn.running_mean, bn.running_var)):
+                if mine.data_ptr() != theirs.data_ptr():
+                    theirs.copy_(mine)
+
+
 def _pad4(x):
     """fp32, contiguous, rows padded to a multiple of 4 floats (the interpolation kernels' 16-byte accesses)."""
     F0 = x.shape[1]
@@ -198,11 +255,8 @@ class _SegmentMax(torch.autograd.Function):
         n, F = xc.shape
         out = torch.empty((nb, F), dtype=torch.float32, device=x.device)
         arg = torch.empty((nb, F), dtype=torch.int32, device=x.device)
-        if xc.dtype == torch.bfloat16:
-            st = lib().p2w_segment_max_arg_bf16(ptr(xc), F, F, ptr(csr), nb, ptr(out), ptr(arg), stream())
-        else:
-            st = lib().p2w_segment_max_arg_io(ptr(xc), _code(xc), F, F, ptr(csr), nb, ptr(out), ptr(arg), stream())
-        check(st, "segment_max_arg")
+        fn, code = _entry("segment_max_arg", xc)
+        check(fn(ptr(xc), *code, F, F, ptr(csr), nb, ptr(out), ptr(arg), stream()), "segment_max_arg")
         ctx.save_for_backward(arg, csr)
         ctx.shape, ctx.dtype, ctx.kernel_dtype = (n, F), x.dtype, xc.dtype
         return out
@@ -213,11 +267,8 @@ class _SegmentMax(torch.autograd.Function):
         n, F = ctx.shape
         g = grad_out.to(torch.float32).contiguous()
         grad_x = torch.empty((n, F), dtype=ctx.kernel_dtype, device=g.device)
-        if grad_x.dtype == torch.bfloat16:
-            st = lib().p2w_segment_max_bwd_bf16(ptr(g), F, ptr(arg), ptr(csr), arg.shape[0], F, ptr(grad_x), F, n, stream())
-        else:
-            st = lib().p2w_segment_max_bwd_io(ptr(g), F, ptr(arg), ptr(csr), arg.shape[0], F, ptr(grad_x), _code(grad_x), F, n, stream())
-        check(st, "segment_max_bwd")
+        fn, code = _entry("segment_max_bwd", grad_x)
+        check(fn(ptr(g), F, ptr(arg), ptr(csr), arg.shape[0], F, ptr(grad_x), *code, F, n, stream()), "segment_max_bwd")
         return grad_x.to(ctx.dtype), None, None
 
     @staticmethod
@@ -231,18 +282,8 @@ class _SegmentMax(torch.autograd.Function):
         return _SegmentMax._backward(ctx, grad_out)
 
 
-class _SegmentMaxHalf(_SegmentMax):
-    """``_SegmentMax`` on a float16 or bfloat16 ``x`` as it is (``half_io``): no fp32 copy of ``x``, ``grad_x`` written in its dtype by the kernel."""
-
-    @staticmethod
-    def forward(ctx, x, csr, nb):
-        with _no_autocast():
-            return _SegmentMax._forward(ctx, x, csr, nb, keeps_half=True)
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        with _no_autocast():
-            return _SegmentMax._backward(ctx, grad_out)
+_SegmentMaxHalf = _half_twin(_SegmentMax, """``_SegmentMax`` on a float16 or bfloat16 ``x`` as it is (``half_io``): no fp32 copy of ``x``,
+    ``grad_x`` written in its dtype by the kernel.""")
 
 
 def global_max_pool(x, batch, size=None):
@@ -296,7 +337,7 @@ class _KnnInterpolate(torch.autograd.Function):
         (n, F0), m = ctx.shape, rf.shape[0]
         g, F = _pad4(grad_out)
         grad_x = torch.empty((n, F), dtype=torch.float32, device=g.device)
-        ws = torch.empty(ws_bytes("interp_bwd", m, ctx.k, n), dtype=torch.uint8, device=g.device)
+        ws = _ws("interp_bwd", m, ctx.k, n, device=g.device)
         check(lib().p2w_interp_bwd(ptr(g), F, F, ptr(rc), ptr(rf), ptr(nbr), ptr(deg), ctx.k, m, n, ptr(grad_x), F,
                                    ptr(ws), ws.numel(), stream()), "knn_interpolate backward")
         if F != F0:
@@ -332,6 +373,29 @@ def _f32c(t):
     return _lib.aligned16(t.detach().to(torch.float32).contiguous())
 
 
+def _edge_l1_backward(ctx, g, recompute):
+    """(grad P, grad Wg, grad pos_src) for both routes of ``edge_layer1``.  What ``ctx`` saved first is the fp32 H1, whose sign is the ReLU
+    mask (``p2w_edge_l1_bwd`` on an fp32 ``g``), or - ``recompute`` - the fp32 P that the mask is computed from once more
+    (``p2w_edge_l1_bwd_io`` on ``g`` in the dtype it came in)."""
+    mask, geo, src, Wg = ctx.saved_tensors
+    n_src, E, C1, dev = ctx.n_src, src.numel(), Wg.shape[1], g.device
+    gP = torch.empty((n_src, C1), dtype=torch.float32, device=dev)
+    gR = torch.empty(n_src, dtype=torch.float32, device=dev)
+    gWg = torch.empty((4, C1), dtype=torch.float32, device=dev)
+    ws = _ws("edge_l1_bwd", E, n_src, C1, device=dev)
+    tail = (ptr(mask), C1, ptr(geo), ptr(src), ptr(Wg), n_src, E, C1, ptr(gP), C1, ptr(gR), ptr(gWg), ptr(ws), ws.numel(), stream())
+    if recompute:
+        check(lib().p2w_edge_l1_bwd_io(ptr(g), _code(g), C1, *tail), "edge_layer1 backward")
+    else:
+        check(lib().p2w_edge_l1_bwd(ptr(g), C1, *tail), "edge_layer1 backward")
+    gpos = None
+    if ctx.needs_input_grad[2]:
+        gpos = torch.zeros((n_src, 4), dtype=torch.float32, device=dev)
+        gpos[:, 3] = gR
+        gpos = gpos.to(ctx.dtypes[2])
+    return gP.to(ctx.dtypes[0]), gWg.to(ctx.dtypes[1]), gpos
+
+
 class _EdgeLayer1(torch.autograd.Function):
     """``p2w_edge_l1`` forward, ``p2w_edge_l1_bwd`` backward: gradients with respect to P, Wg and column 3 of ``pos_src``.
     H1 (the ReLU mask) and geo are saved for backward only."""
@@ -349,21 +413,7 @@ class _EdgeLayer1(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_H1, _grad_geo):
-        H1, geo, src, Wg = ctx.saved_tensors
-        (E, C1), n_src, dev = H1.shape, ctx.n_src, H1.device
-        g = _f32c(grad_H1)
-        gP = torch.empty((n_src, C1), dtype=torch.float32, device=dev)
-        gR = torch.empty(n_src, dtype=torch.float32, device=dev)
-        gWg = torch.empty((4, C1), dtype=torch.float32, device=dev)
-        ws = torch.empty(ws_bytes("edge_l1_bwd", E, n_src, C1), dtype=torch.uint8, device=dev)
-        check(lib().p2w_edge_l1_bwd(ptr(g), C1, ptr(H1), C1, ptr(geo), ptr(src), ptr(Wg), n_src, E, C1, ptr(gP), C1, ptr(gR), ptr(gWg),
-                                    ptr(ws), ws.numel(), stream()), "edge_layer1 backward")
-        gpos = None
-        if ctx.needs_input_grad[2]:
-            gpos = torch.zeros((n_src, 4), dtype=torch.float32, device=dev)
-            gpos[:, 3] = gR
-            gpos = gpos.to(ctx.dtypes[2])
-        return gP.to(ctx.dtypes[0]), gWg.to(ctx.dtypes[1]), gpos, None, None, None
+        return (*_edge_l1_backward(ctx, _f32c(grad_H1), recompute=False), None, None, None)
 
 
 class _EdgeLayer1Half(torch.autograd.Function):
@@ -377,28 +427,15 @@ class _EdgeLayer1Half(torch.autograd.Function):
             Pc, Wc = _f32c(P), _f32c(Wg)
             geo, H1 = _edge_l1_forward(Pc, Wc, _f32c(pos_src), rd, csr, src, out_dtype)
             ctx.save_for_backward(Pc, geo, src, Wc)
-            ctx.dtypes = (P.dtype, Wg.dtype, pos_src.dtype)
+            ctx.n_src, ctx.dtypes = P.shape[0], (P.dtype, Wg.dtype, pos_src.dtype)
             ctx.mark_non_differentiable(geo)
             return H1, geo
 
     @staticmethod
     def backward(ctx, grad_H1, _grad_geo):
         with _no_autocast():
-            P, geo, src, Wg = ctx.saved_tensors
-            (n_src, C1), E, dev = P.shape, src.numel(), P.device
             g = _lib.aligned16(grad_H1.detach().contiguous()) if grad_H1.dtype in _HALF_TYPES else _f32c(grad_H1)
-            gP = torch.empty((n_src, C1), dtype=torch.float32, device=dev)
-            gR = torch.empty(n_src, dtype=torch.float32, device=dev)
-            gWg = torch.empty((4, C1), dtype=torch.float32, device=dev)
-            ws = torch.empty(ws_bytes("edge_l1_bwd", E, n_src, C1), dtype=torch.uint8, device=dev)
-            check(lib().p2w_edge_l1_bwd_io(ptr(g), _code(g), C1, ptr(P), C1, ptr(geo), ptr(src), ptr(Wg), n_src, E, C1, ptr(gP), C1, ptr(gR),
-                                           ptr(gWg), ptr(ws), ws.numel(), stream()), "edge_layer1 backward")
-            gpos = None
-            if ctx.needs_input_grad[2]:
-                gpos = torch.zeros((n_src, 4), dtype=torch.float32, device=dev)
-                gpos[:, 3] = gR
-                gpos = gpos.to(ctx.dtypes[2])
-            return gP.to(ctx.dtypes[0]), gWg.to(ctx.dtypes[1]), gpos, None, None, None, None
+            return (*_edge_l1_backward(ctx, g, recompute=True), None, None, None, None)
 
 
 def edge_layer1(P, Wg, pos_src, pos_dst, edge_index, out_dtype=None):
@@ -442,14 +479,12 @@ def _relu_bn_max_forward(zc, gamma, beta, csr, M, bn):
     out, ext = (torch.empty((M, C2), dtype=torch.float32, device=dev) for _ in range(2))
     arg = torch.empty((M, C2), dtype=torch.int32, device=dev)
     mean, invstd = (torch.empty(C2, dtype=torch.float32, device=dev) for _ in range(2))
-    rm, rv = (t.detach().to(torch.float32).contiguous() for t in (bn.running_mean, bn.running_var))
-    ws = torch.empty(ws_bytes("relu_bn_max", E, M, C2), dtype=torch.uint8, device=dev)
+    running = _running([bn])
+    rm, rv = running[0]
+    ws = _ws("relu_bn_max", E, M, C2, device=dev)
     check(lib().p2w_relu_bn_max_io(ptr(zc), _code(zc), C2, ptr(csr), ptr(gamma), ptr(beta), ptr(rm), ptr(rv), float(bn.momentum), float(bn.eps),
                                    E, M, C2, ptr(out), ptr(ext), ptr(arg), ptr(mean), ptr(invstd), ptr(ws), ws.numel(), stream()), "relu_bn_max")
-    with torch.no_grad():
-        for mine, theirs in ((rm, bn.running_mean), (rv, bn.running_var)):
-            if mine.data_ptr() != theirs.data_ptr():
-                theirs.copy_(mine)
+    _write_back([bn], running)
     return out, ext, arg, mean, invstd
 
 
@@ -472,7 +507,7 @@ class _ReluBnMax(torch.autograd.Function):
         g = _f32c(grad_out)
         dz = torch.empty((E, C2), dtype=z.dtype, device=dev)
         dgamma, dbeta = (torch.empty(C2, dtype=torch.float32, device=dev) for _ in range(2))
-        ws = torch.empty(ws_bytes("relu_bn_max", E, M, C2), dtype=torch.uint8, device=dev)
+        ws = _ws("relu_bn_max", E, M, C2, device=dev)
         check(lib().p2w_relu_bn_max_bwd_io(ptr(g), ptr(z), _code(z), C2, ptr(csr), ptr(arg), ptr(ext), ptr(mean), ptr(invstd), ptr(gamma), E, M,
                                            C2, ptr(dz), C2, ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), stream()), "relu_bn_max backward")
         return dz.to(ctx.dtypes[0]), dgamma.to(ctx.dtypes[1]), dbeta.to(ctx.dtypes[2]), None, None, None
@@ -488,30 +523,16 @@ class _ReluBnMax(torch.autograd.Function):
         return _ReluBnMax._backward(ctx, grad_out)
 
 
-class _ReluBnMaxHalf(_ReluBnMax):
-    """``_ReluBnMax`` on a float16 or bfloat16 ``z`` as it is (``half_io``): ``z`` itself is saved - no fp32 copy of it - the output stays
-    fp32 and ``dz`` is written in ``z``'s dtype by the kernel."""
-
-    @staticmethod
-    def forward(ctx, z, gamma, beta, csr, M, bn):
-        with _no_autocast():
-            return _ReluBnMax._forward(ctx, z, gamma, beta, csr, M, bn, keeps_half=True)
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        with _no_autocast():
-            return _ReluBnMax._backward(ctx, grad_out)
+_ReluBnMaxHalf = _half_twin(_ReluBnMax, """``_ReluBnMax`` on a float16 or bfloat16 ``z`` as it is (``half_io``): ``z`` itself is saved - no fp32
+    copy of it - the output stays fp32 and ``dz`` is written in ``z``'s dtype by the kernel.""")
 
 
 def _relu_bn_max_sorted(z, index, bn, M):
     """``relu_bn_max`` on an index that is known to be ascending and inside [0, M)."""
     if not bn.training:
         return scatter_max(bn(torch.relu(z)), index, dim=0, dim_size=M)[0]
-    if z.shape[0] < 2:
-        raise ValueError(f"Expected more than 1 value per channel when training, got input size {z.size()}")
+    _training_tick(z, [bn])
     csr = torch.searchsorted(index.to(torch.int64).contiguous(), torch.arange(M + 1, device=index.device, dtype=torch.int64)).to(torch.int32)
-    if bn.num_batches_tracked is not None:
-        bn.num_batches_tracked.add_(1)
     if torch.is_grad_enabled() and (z.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad):
         return (_ReluBnMaxHalf if _keeps_half(z) else _ReluBnMax).apply(z, bn.weight, bn.bias, csr, M, bn)
     zc = z.detach().contiguous() if _keeps_half(z) else _f32c(z)
@@ -543,10 +564,7 @@ def relu_bn_max(z, index, bn, dim_size=None):
     ``track_running_stats=False`` and ``momentum=None`` raise ``NotImplementedError`` (the reference builds none of them); fewer than
     two rows in training mode raise PyTorch's ``ValueError``."""
     _lib.require_cuda(z, index)
-    if not isinstance(bn, torch.nn.BatchNorm1d):
-        raise TypeError("relu_bn_max: bn must be a torch.nn.BatchNorm1d")
-    if not bn.affine or not bn.track_running_stats or bn.momentum is None:
-        raise NotImplementedError("relu_bn_max supports BatchNorm1d(affine=True, track_running_stats=True, momentum=<float>) as the reference builds it")
+    _check_bn(bn, "relu_bn_max")
     if z.dim() != 2 or z.shape[1] != bn.num_features or index.dim() != 1 or index.numel() != z.shape[0]:
         raise RuntimeError("relu_bn_max: z [E, C] with C = bn.num_features, index [E]")
     i = index.to(torch.int64)
@@ -754,28 +772,18 @@ def _chain_stage_array(meta, vec, running):
     return arr
 
 
-def _chain_ws(M, C, L, dev):
-    need = int(lib().p2w_bn_chain_ws_size(M, C, L))
-    if need == 0:
-        raise RuntimeError(f"p2w_bn_chain_ws_size({M}, {C}, {L}) failed")
-    return torch.empty(need, dtype=torch.uint8, device=dev)
-
-
 def _bn_chain_forward(zc, rc, meta, vec, out_dtype=torch.float32):
     """(out, mean, invstd) of ``p2w_bn_chain_io`` on a contiguous fp32, float16 or bfloat16 z (everything else fp32, contiguous); every bn's
     running statistics move in place."""
     (M, C), L, dev = zc.shape, len(meta), zc.device
     out = torch.empty((M, C), dtype=out_dtype, device=dev)
     mean, invstd = (torch.empty((L, C), dtype=torch.float32, device=dev) for _ in range(2))
-    running = [tuple(t.detach().to(torch.float32).contiguous() for t in (bn.running_mean, bn.running_var)) for bn, _, _ in meta]
-    ws = _chain_ws(M, C, L, dev)
+    bns = [bn for bn, _, _ in meta]
+    running = _running(bns)
+    ws = _ws("bn_chain", M, C, L, device=dev)
     check(lib().p2w_bn_chain_io(ptr(zc), _code(zc), C, ptr(rc), C, _chain_stage_array(meta, vec, running), L, M, C, ptr(out), _code(out), C,
                                 ptr(mean), ptr(invstd), ptr(ws), ws.numel(), stream()), "bn_chain")
-    with torch.no_grad():
-        for (bn, _, _), (rm, rv) in zip(meta, running):
-            for mine, theirs in ((rm, bn.running_mean), (rv, bn.running_var)):
-                if mine.data_ptr() != theirs.data_ptr():
-                    theirs.copy_(mine)
+    _write_back(bns, running)
     return out, mean, invstd
 
 
@@ -786,7 +794,7 @@ class _BnChain(torch.autograd.Function):
     to a depthwise bias is exactly zero: BatchNorm subtracts the column mean, which removes any bias added in front of it."""
 
     @staticmethod
-    def _forward(ctx, z, residual, meta, params, out_dtype=torch.float32, keeps_half=False):
+    def _forward(ctx, z, residual, meta, out_dtype, *params, keeps_half=False):
         zc = z.detach().contiguous() if keeps_half else _f32c(z)
         rc = None if residual is None else _f32c(residual)
         vec = [_f32c(p.reshape(-1)) for p in params]
@@ -798,8 +806,8 @@ class _BnChain(torch.autograd.Function):
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, z, residual, meta, *params):          # (meta holds modules and flags, no tensors: custom_fwd passes it through)
-        return _BnChain._forward(ctx, z, residual, meta, params)
+    def forward(ctx, z, residual, meta, out_dtype, *params):   # (meta holds modules and flags, no tensors: custom_fwd passes it through)
+        return _BnChain._forward(ctx, z, residual, meta, out_dtype, *params)
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
@@ -819,7 +827,7 @@ class _BnChain(torch.autograd.Function):
         dgamma, dbeta = (torch.empty((L, C), dtype=torch.float32, device=dev) for _ in range(2))
         any_dw = any(m[2] for m in meta)
         ddw_w, ddw_b = (torch.empty((L, C), dtype=torch.float32, device=dev) for _ in range(2)) if any_dw else (None, None)
-        ws = _chain_ws(M, C, L, dev)
+        ws = _ws("bn_chain", M, C, L, device=dev)
         check(lib().p2w_bn_chain_bwd_io(ptr(g), _code(g), C, ptr(z), _code(z), C, ptr(out), C, _chain_stage_array(meta, vec, None), L, ptr(mean),
                                         ptr(invstd), M, C, ptr(dz), C, ptr(dres), C, ptr(dgamma), ptr(dbeta), ptr(ddw_w), ptr(ddw_b), ptr(ws),
                                         ws.numel(), stream()), "bn_chain backward")
@@ -828,34 +836,19 @@ class _BnChain(torch.autograd.Function):
             grads += [dgamma[t], dbeta[t]] + ([ddw_w[t], ddw_b[t]] if has_dw else [])
         like = ctx.like
         grads = [gr.to(dt).reshape(shape) for gr, (dt, shape) in zip(grads, like[1:1 + n_vec])]
-        return (dz.to(like[0][0]), None if dres is None else dres.to(like[-1][0]), None, *grads)
+        return (dz.to(like[0][0]), None if dres is None else dres.to(like[-1][0]), None, None, *grads)
 
 
-class _BnChainHalf(_BnChain):
-    """``_BnChain`` on a float16 or bfloat16 ``z`` as it is (``half_io``): ``z`` itself is saved, the output is fp32 or ``z``'s dtype, its
-    gradient is read in the dtype it arrives in and ``dz`` is written in ``z``'s dtype by the kernel.  Parameters, the residual and the saved output of a chain
-    with a residual stay fp32."""
-
-    @staticmethod
-    def forward(ctx, z, residual, meta, out_dtype, *params):
-        with _no_autocast():
-            return _BnChain._forward(ctx, z, residual, meta, params, out_dtype, keeps_half=True)
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        with _no_autocast():
-            grads = _BnChain._backward(ctx, grad_out)
-        return (*grads[:3], None, *grads[3:])
+_BnChainHalf = _half_twin(_BnChain, """``_BnChain`` on a float16 or bfloat16 ``z`` as it is (``half_io``): ``z`` itself is saved, the output is fp32
+    or ``z``'s dtype, its gradient is read in the dtype it arrives in and ``dz`` is written in ``z``'s dtype by the kernel.  Parameters, the
+    residual and the saved output of a chain with a residual stay fp32.""")
 
 
 def _chain_normalise(stages, C, who="bn_chain"):
     meta = []
     for st in stages:
         bn, relu, dw = st if len(st) == 3 else (*st, None)
-        if not isinstance(bn, torch.nn.BatchNorm1d):
-            raise TypeError(f"{who}: every stage is (BatchNorm1d, relu) or (BatchNorm1d, relu, depthwise Conv1d or None)")
-        if not bn.affine or not bn.track_running_stats or bn.momentum is None:
-            raise NotImplementedError(f"{who} supports BatchNorm1d(affine=True, track_running_stats=True, momentum=<float>) as the reference builds it")
+        _check_bn(bn, who, f"{who}: every stage is (BatchNorm1d, relu) or (BatchNorm1d, relu, depthwise Conv1d or None)")
         if bn.num_features != C:
             raise RuntimeError(f"{who}: z [M, C] with C = num_features of every BatchNorm1d")
         if dw is not None:
@@ -928,11 +921,7 @@ def bn_chain(z, stages, residual=None, out_dtype=None):
                 x = torch.relu(x)
         x = x if residual is None else torch.relu(x + residual)
         return x.to(out_dtype) if out_dtype in _HALF_TYPES else x
-    if z.shape[0] < 2:
-        raise ValueError(f"Expected more than 1 value per channel when training, got input size {z.size()}")
-    for bn, _, _ in meta:
-        if bn.num_batches_tracked is not None:
-            bn.num_batches_tracked.add_(1)
+    _training_tick(z, [bn for bn, _, _ in meta])
     params = []
     for bn, _, dw in meta:
         params += [bn.weight, bn.bias] + ([dw.weight, dw.bias] if dw is not None else [])
@@ -940,7 +929,7 @@ def bn_chain(z, stages, residual=None, out_dtype=None):
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (z, residual, *params)):
         if _keeps_half(z):
             return _BnChainHalf.apply(z, residual, flags, out_dtype, *params)
-        return _BnChain.apply(z, residual, flags, *params).to(out_dtype)
+        return _BnChain.apply(z, residual, flags, torch.float32, *params).to(out_dtype)
     return _bn_chain_forward(_f32c(z), None if residual is None else _f32c(residual), flags, [_f32c(p.reshape(-1)) for p in params])[0].to(out_dtype)
 
 
@@ -1056,10 +1045,7 @@ class _InterpAddRelu(torch.autograd.Function):
         g = _lib.aligned16(_pad4(grad_out)[0])
         dS = torch.empty((m, C), dtype=torch.float32, device=dev)
         dPc = torch.empty((n_c, C), dtype=torch.float32, device=dev)
-        need = int(lib().p2w_interp_add_relu_bwd_ws_size(m, ctx.k, n_c))
-        if need == 0:
-            raise RuntimeError(f"p2w_interp_add_relu_bwd_ws_size({m}, {ctx.k}, {n_c}) failed")
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = _ws("interp_add_relu_bwd", m, ctx.k, n_c, device=dev)
         check(lib().p2w_interp_add_relu_bwd(ptr(g), C, ptr(H), C, ptr(rc), ptr(rf), ptr(nbr), ptr(deg), ctx.k, m, n_c, C, ptr(dS), C, ptr(dPc), C,
                                             ptr(ws), ws.numel(), stream()), "interp_add_relu backward")
         if C != C0:
@@ -1095,27 +1081,18 @@ def interp_add_relu(Pc, S, pos_x, pos_y, batch_x=None, batch_y=None, k=3):
     return H if H.shape[1] == S.shape[1] else H[:, :S.shape[1]].contiguous()
 
 
-def _relu_bn_ws(M, C, dev):
-    need = int(lib().p2w_relu_bn_ws_size(M, C))
-    if need == 0:
-        raise RuntimeError(f"p2w_relu_bn_ws_size({M}, {C}) failed")
-    return torch.empty(need, dtype=torch.uint8, device=dev)
-
-
 def _relu_bn_forward(zc, gamma, beta, bn, out_dtype=torch.float32):
     """(out, mean, invstd) of ``p2w_relu_bn_io`` on a contiguous fp32, float16 or bfloat16 z (the vectors fp32); bn's running statistics move in
     place."""
     (M, C), dev = zc.shape, zc.device
     out = torch.empty((M, C), dtype=out_dtype, device=dev)
     mean, invstd = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(2))
-    rm, rv = (t.detach().to(torch.float32).contiguous() for t in (bn.running_mean, bn.running_var))
-    ws = _relu_bn_ws(M, C, dev)
+    running = _running([bn])
+    rm, rv = running[0]
+    ws = _ws("relu_bn", M, C, device=dev)
     check(lib().p2w_relu_bn_io(ptr(zc), _code(zc), C, ptr(gamma), ptr(beta), ptr(rm), ptr(rv), float(bn.momentum), float(bn.eps), M, C, ptr(out),
                                _code(out), C, ptr(mean), ptr(invstd), ptr(ws), ws.numel(), stream()), "relu_bn")
-    with torch.no_grad():
-        for mine, theirs in ((rm, bn.running_mean), (rv, bn.running_var)):
-            if mine.data_ptr() != theirs.data_ptr():
-                theirs.copy_(mine)
+    _write_back([bn], running)
     return out, mean, invstd
 
 
@@ -1124,7 +1101,7 @@ class _ReluBn(torch.autograd.Function):
     invstd and gamma - no [M, C] tensor besides z itself."""
 
     @staticmethod
-    def _forward(ctx, z, gamma, beta, bn, out_dtype=torch.float32, keeps_half=False):
+    def _forward(ctx, z, gamma, beta, bn, out_dtype, keeps_half=False):
         zc, gc = z.detach().contiguous() if keeps_half else _f32c(z), _f32c(gamma)
         out, mean, invstd = _relu_bn_forward(zc, gc, _f32c(beta), bn, out_dtype)
         ctx.save_for_backward(zc, mean, invstd, gc)
@@ -1138,15 +1115,15 @@ class _ReluBn(torch.autograd.Function):
         g = _grad_for(grad_out, z)
         dz = torch.empty((M, C), dtype=z.dtype, device=dev)
         dgamma, dbeta = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(2))
-        ws = _relu_bn_ws(M, C, dev)
+        ws = _ws("relu_bn", M, C, device=dev)
         check(lib().p2w_relu_bn_bwd_io(ptr(g), _code(g), C, ptr(z), _code(z), C, ptr(gamma), ptr(mean), ptr(invstd), M, C, ptr(dz), C, ptr(dgamma),
                                        ptr(dbeta), ptr(ws), ws.numel(), stream()), "relu_bn backward")
-        return dz.to(ctx.dtypes[0]), dgamma.to(ctx.dtypes[1]), dbeta.to(ctx.dtypes[2]), None
+        return dz.to(ctx.dtypes[0]), dgamma.to(ctx.dtypes[1]), dbeta.to(ctx.dtypes[2]), None, None
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, z, gamma, beta, bn):
-        return _ReluBn._forward(ctx, z, gamma, beta, bn)
+    def forward(ctx, z, gamma, beta, bn, out_dtype):
+        return _ReluBn._forward(ctx, z, gamma, beta, bn, out_dtype)
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
@@ -1154,19 +1131,8 @@ class _ReluBn(torch.autograd.Function):
         return _ReluBn._backward(ctx, grad_out)
 
 
-class _ReluBnHalf(_ReluBn):
-    """``_ReluBn`` on a float16 or bfloat16 ``z`` as it is (``half_io``): ``z`` itself is saved, the output is fp32 or ``z``'s dtype, its
-    gradient is read in the dtype it arrives in and ``dz`` is written in ``z``'s dtype by the kernel."""
-
-    @staticmethod
-    def forward(ctx, z, gamma, beta, bn, out_dtype):
-        with _no_autocast():
-            return _ReluBn._forward(ctx, z, gamma, beta, bn, out_dtype, keeps_half=True)
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        with _no_autocast():
-            return (*_ReluBn._backward(ctx, grad_out), None)
+_ReluBnHalf = _half_twin(_ReluBn, """``_ReluBn`` on a float16 or bfloat16 ``z`` as it is (``half_io``): ``z`` itself is saved, the output is fp32 or
+    ``z``'s dtype, its gradient is read in the dtype it arrives in and ``dz`` is written in ``z``'s dtype by the kernel.""")
 
 
 def relu_bn(z, bn, out_dtype=None):
@@ -1185,53 +1151,36 @@ def relu_bn(z, bn, out_dtype=None):
     In eval mode this is ``bn(torch.relu(z))`` itself.  ``affine=False``, ``track_running_stats=False`` and ``momentum=None`` raise
     ``NotImplementedError``; fewer than two rows in training mode raise PyTorch's ``ValueError``."""
     _lib.require_cuda(z)
-    if not isinstance(bn, torch.nn.BatchNorm1d):
-        raise TypeError("relu_bn: bn must be a torch.nn.BatchNorm1d")
-    if not bn.affine or not bn.track_running_stats or bn.momentum is None:
-        raise NotImplementedError("relu_bn supports BatchNorm1d(affine=True, track_running_stats=True, momentum=<float>) as the reference builds it")
+    _check_bn(bn, "relu_bn")
     if z.dim() != 2 or z.shape[1] != bn.num_features:
         raise RuntimeError("relu_bn: z [M, C] with C = bn.num_features")
     out_dtype = _out_dtype(out_dtype, z, "relu_bn")
     if not bn.training:
         x = bn(torch.relu(z))
         return x.to(out_dtype) if out_dtype in _HALF_TYPES else x
-    if z.shape[0] < 2:
-        raise ValueError(f"Expected more than 1 value per channel when training, got input size {z.size()}")
-    if bn.num_batches_tracked is not None:
-        bn.num_batches_tracked.add_(1)
+    _training_tick(z, [bn])
     if torch.is_grad_enabled() and (z.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad):
         if _keeps_half(z):
             return _ReluBnHalf.apply(z, bn.weight, bn.bias, bn, out_dtype)
-        return _ReluBn.apply(z, bn.weight, bn.bias, bn).to(out_dtype)
+        return _ReluBn.apply(z, bn.weight, bn.bias, bn, torch.float32).to(out_dtype)
     return _relu_bn_forward(_f32c(z), _f32c(bn.weight), _f32c(bn.bias), bn)[0].to(out_dtype)
 
 
 # --------------------------------------------------------------------------- the head behind conv1 for training
-def _head_ws(M, C, dev):
-    need = int(lib().p2w_bn_relu_rowdot_ws_size(M, C))
-    if need == 0:
-        raise RuntimeError(f"p2w_bn_relu_rowdot_ws_size({M}, {C}) failed")
-    return torch.empty(need, dtype=torch.uint8, device=dev)
-
-
 def _bn_relu_rowdot_forward(zc, gamma, beta, w, b, bn):
     """(logit, mean, invstd) of ``p2w_bn_relu_rowdot_io`` (``_bf16``) on a contiguous fp32 or float16 (bfloat16) z (the vectors fp32); bn's running statistics
     move in place."""
     (M, C), dev = zc.shape, zc.device
     logit = torch.empty(M, dtype=torch.float32, device=dev)
     mean, invstd = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(2))
-    rm, rv = (t.detach().to(torch.float32).contiguous() for t in (bn.running_mean, bn.running_var))
-    ws = _head_ws(M, C, dev)
+    running = _running([bn])
+    rm, rv = running[0]
+    ws = _ws("bn_relu_rowdot", M, C, device=dev)
     tail = (ptr(gamma), ptr(beta), ptr(w), ptr(b), ptr(rm), ptr(rv), float(bn.momentum), float(bn.eps), M, C, ptr(logit), ptr(mean), ptr(invstd),
             ptr(ws), ws.numel(), stream())
-    if zc.dtype == torch.bfloat16:
-        check(lib().p2w_bn_relu_rowdot_bf16(ptr(zc), C, *tail), "bn_relu_rowdot")
-    else:
-        check(lib().p2w_bn_relu_rowdot_io(ptr(zc), _code(zc), C, *tail), "bn_relu_rowdot")
-    with torch.no_grad():
-        for mine, theirs in ((rm, bn.running_mean), (rv, bn.running_var)):
-            if mine.data_ptr() != theirs.data_ptr():
-                theirs.copy_(mine)
+    fn, code = _entry("bn_relu_rowdot", zc)
+    check(fn(ptr(zc), *code, C, *tail), "bn_relu_rowdot")
+    _write_back([bn], running)
     return logit, mean, invstd
 
 
@@ -1266,29 +1215,16 @@ class _BnReluRowdot(torch.autograd.Function):
         dz = torch.empty((M, C), dtype=z.dtype, device=dev)
         dgamma, dbeta, dw = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(3))
         dbias = torch.empty(1, dtype=torch.float32, device=dev)
-        ws = _head_ws(M, C, dev)
+        ws = _ws("bn_relu_rowdot", M, C, device=dev)
         tail = (ptr(gamma), ptr(beta), ptr(w), ptr(mean), ptr(invstd), M, C, ptr(dz), C, ptr(dgamma), ptr(dbeta), ptr(dw), ptr(dbias), ptr(ws),
                 ws.numel(), stream())
-        if z.dtype == torch.bfloat16:
-            check(lib().p2w_bn_relu_rowdot_bwd_bf16(ptr(g), ptr(z), C, *tail), "bn_relu_rowdot backward")
-        else:
-            check(lib().p2w_bn_relu_rowdot_bwd_io(ptr(g), ptr(z), _code(z), C, *tail), "bn_relu_rowdot backward")
+        fn, code = _entry("bn_relu_rowdot_bwd", z)
+        check(fn(ptr(g), ptr(z), *code, C, *tail), "bn_relu_rowdot backward")
         return (*[gr.to(dt).reshape(shape) for gr, (dt, shape) in zip((dz, dgamma, dbeta, dw, dbias), ctx.like)], None)
 
 
-class _BnReluRowdotHalf(_BnReluRowdot):
-    """``_BnReluRowdot`` on a float16 or bfloat16 ``z`` as it is (``half_io``): ``z`` itself is saved and ``dz`` is written in its dtype by the kernel;
-    the logits and their gradient stay fp32."""
-
-    @staticmethod
-    def forward(ctx, z, gamma, beta, weight, bias, bn):
-        with _no_autocast():
-            return _BnReluRowdot._forward(ctx, z, gamma, beta, weight, bias, bn, keeps_half=True)
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        with _no_autocast():
-            return _BnReluRowdot._backward(ctx, grad_out)
+_BnReluRowdotHalf = _half_twin(_BnReluRowdot, """``_BnReluRowdot`` on a float16 or bfloat16 ``z`` as it is (``half_io``): ``z`` itself is saved and
+    ``dz`` is written in its dtype by the kernel; the logits and their gradient stay fp32.""")
 
 
 def bn_relu_rowdot(z, bn, weight, bias):
@@ -1309,11 +1245,7 @@ def bn_relu_rowdot(z, bn, weight, bias):
     In eval mode this is the plain composition on the running statistics.  ``affine=False``, ``track_running_stats=False`` and
     ``momentum=None`` raise ``NotImplementedError``; fewer than two rows in training mode raise PyTorch's ``ValueError``."""
     _lib.require_cuda(z, weight, bias)
-    if not isinstance(bn, torch.nn.BatchNorm1d):
-        raise TypeError("bn_relu_rowdot: bn must be a torch.nn.BatchNorm1d")
-    if not bn.affine or not bn.track_running_stats or bn.momentum is None:
-        raise NotImplementedError("bn_relu_rowdot supports BatchNorm1d(affine=True, track_running_stats=True, momentum=<float>) as the "
-                                  "reference builds it")
+    _check_bn(bn, "bn_relu_rowdot")
     if z.dim() != 2 or z.shape[1] != bn.num_features:
         raise RuntimeError("bn_relu_rowdot: z [M, C] with C = bn.num_features")
     C = z.shape[1]
@@ -1321,10 +1253,7 @@ def bn_relu_rowdot(z, bn, weight, bias):
         raise RuntimeError("bn_relu_rowdot: weight [1, C] or [1, C, 1] and a bias of one element (one output channel)")
     if not bn.training:
         return torch.nn.functional.linear(torch.relu(bn(z)), weight.reshape(1, C), bias.reshape(1))[:, 0]
-    if z.shape[0] < 2:
-        raise ValueError(f"Expected more than 1 value per channel when training, got input size {z.size()}")
-    if bn.num_batches_tracked is not None:
-        bn.num_batches_tracked.add_(1)
+    _training_tick(z, [bn])
     if torch.is_grad_enabled() and any(t.requires_grad for t in (z, bn.weight, bn.bias, weight, bias)):
         return (_BnReluRowdotHalf if _keeps_half(z) else _BnReluRowdot).apply(z, bn.weight, bn.bias, weight, bias, bn)
     return _bn_relu_rowdot_forward(_f32c(z), _f32c(bn.weight), _f32c(bn.bias), _lib.aligned16(_f32c(weight.reshape(-1))),
@@ -1396,10 +1325,7 @@ def random_subset(n, k, seed, counter=(0, 0), device="cuda", keys=None, return_k
         idx = torch.empty(k, dtype=torch.int64, device=device)
         keys_out = torch.empty(n, dtype=torch.int32, device=device) if return_keys else None
         if n > 0 and k > 0:
-            need = int(lib().p2w_random_subset_ws_size(n))
-            if need == 0:
-                raise RuntimeError(f"p2w_random_subset_ws_size({n}) failed")
-            ws = torch.empty(need, dtype=torch.uint8, device=device)
+            ws = _ws("random_subset", n, device=device)
             check(lib().p2w_random_subset(n, k, seed & 0xffffffffffffffff, c1 & 0xffffffff, c2 & 0xffffffff, ptr(keys), ptr(idx),
                                           ptr(keys_out), ptr(ws), ws.numel(), stream()), "p2w_random_subset")
         elif return_keys and n > 0:                              # k = 0 launches nothing: the keys come from a draw of one row
@@ -1443,12 +1369,7 @@ def cap_subset(n, seg_start, seg_count, k, seed, counter=(0, 0), weight=None, ro
         idx = torch.empty((S, k), dtype=torch.int64, device=device)
         keys_out = torch.empty(n, dtype=torch.int32, device=device) if return_keys else None
         if S > 0:
-            ws = None
-            if select:
-                need = int(lib().p2w_cap_subset_ws_size(n, S))
-                if need == 0:
-                    raise RuntimeError(f"p2w_cap_subset_ws_size({n}, {S}) failed")
-                ws = torch.empty(need, dtype=torch.uint8, device=device)
+            ws = _ws("cap_subset", n, S, device=device) if select else None
             check(lib().p2w_cap_subset(n, ptr(seg_start), ptr(seg_count), S, k, ptr(weight), ptr(row_id), seed & 0xffffffffffffffff,
                                        c1 & 0xffffffff, c2 & 0xffffffff, ptr(keys), ptr(idx), ptr(keys_out), ptr(ws),
                                        0 if ws is None else ws.numel(), stream()), "p2w_cap_subset")
