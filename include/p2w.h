@@ -191,7 +191,11 @@ int32_t p2w_ball_query_grid_indexed(const float* xyzr_x, const uint64_t* keys_x,
 
 /* order_out[i] = index of the i-th record in ascending Morton (Z-curve) order of its cell in `grid` (21 bits per
  * axis, cells clamped to the grid): consecutive records are close in all three dimensions - the query order for
- * P2W_SEARCH_BOX searches over a plot.  ws: p2w_morton_order_ws_bytes(n). */
+ * P2W_SEARCH_BOX searches over a plot.  A cell is floor((v - lo) / res) per axis in fp32, below 0 -> 0, above 2^21 - 1 -> 2^21 - 1,
+ * NaN -> 0; bit b of axis a goes to bit 3 b + a of the key (x lowest); records of equal keys keep their input order.
+ * xyzr[n][4], ws: 16-byte aligned, p2w_morton_order_ws_bytes(n) bytes.
+ * Status: n == 0 -> P2W_OK (nothing is read); a NULL xyzr / grid / order_out / ws -> P2W_ENULL; xyzr or ws not 16-byte aligned ->
+ * P2W_EALIGN; n < 0 -> P2W_EINVAL; ws_bytes too small -> P2W_EWORKSPACE (order_out is not written). */
 size_t p2w_morton_order_ws_bytes(int32_t n);
 int32_t p2w_morton_order(const float* xyzr, int32_t n, const p2w_grid* grid, int32_t* order_out, void* ws, size_t ws_bytes,
                          p2w_stream_t stream);
@@ -224,7 +228,10 @@ int32_t p2w_key_runs(const uint64_t* keys_sorted, int32_t n, int32_t min_count, 
  * (n_cells + 1 entries; n_cells = dims[0] * dims[1] * dims[2] of the p2w_grid the keys were made on, times the voxel count).  It is
  * the cell_start argument of p2w_knn_grid_indexed / p2w_ball_query_grid_indexed for levels that did not come from the table sampler -
  * the back-projection's search over all classified points of a plot (predicter.py:129-142: the reference's KD-tree): one load per
- * search run instead of a bisection of the keys.  n_cells < 2^31 - 1.  ws: 16-byte aligned, p2w_cell_starts_ws_bytes(n_cells) bytes. */
+ * search run instead of a bisection of the keys.  n_cells < 2^31 - 1.  ws: 16-byte aligned, p2w_cell_starts_ws_bytes(n_cells) bytes.
+ * n == 0 (keys_sorted may then be NULL) still writes the table: all zeros.
+ * Status: a NULL table_out / ws (or keys_sorted with n > 0) -> P2W_ENULL; ws not 16-byte aligned -> P2W_EALIGN; n < 0, n_cells < 0 or
+ * n_cells >= 2^31 - 1 -> P2W_EINVAL; ws_bytes too small -> P2W_EWORKSPACE. */
 size_t p2w_cell_starts_ws_bytes(int64_t n_cells);
 int32_t p2w_cell_starts(const uint64_t* keys_sorted, int32_t n, int64_t n_cells, int32_t* table_out, void* ws, size_t ws_bytes,
                         p2w_stream_t stream);
@@ -236,7 +243,11 @@ int32_t p2w_cell_starts(const uint64_t* keys_sorted, int32_t n, int64_t n_cells,
  * inverse; keys_sorted / cell_start (optional) / grid: as p2w_knn_grid_indexed; (ox, oy, oz): the offset that was subtracted
  * from the float64 coordinates to make the fp32 ones the grid was built on; q[m][3]: float64 queries.  nbr[m, k] / deg[m]: in
  * = any k candidates per query (the fp32 result; deg < k only where fewer than k candidates exist), out = the k nearest in
- * float64, ascending (squared distance = ((dx^2 + dy^2) + dz^2), candidate index).  k <= P2W_MAX_K. */
+ * float64, ascending (squared distance = ((dx^2 + dy^2) + dz^2), candidate index).  k <= P2W_MAX_K.
+ * A row with deg < k comes back with its deg entries in that order, the slots behind them and deg unchanged; a row with deg <= 0
+ * is left alone.
+ * Status: m == 0 or nc == 0 -> P2W_OK (nothing is read); a NULL pointer other than cell_start -> P2W_ENULL; m < 0, nc < 0, k < 1 or
+ * k > P2W_MAX_K -> P2W_EINVAL. */
 int32_t p2w_knn_refine_f64(const double* cand_sorted, const int32_t* cand_index, const int32_t* cand_pos,
                            const uint64_t* keys_sorted, const int32_t* cell_start, const p2w_grid* grid, double ox, double oy,
                            double oz, const double* q, int32_t m, int32_t nc, int32_t k, int32_t* nbr, int32_t* deg,
@@ -551,7 +562,11 @@ int32_t p2w_clip_adamw(const p2w_optim_tensor* tensors, int32_t T, const p2w_opt
 /* PointCloudClassifier.compute_labels (predicter.py:112-127) over a neighbour table nbr[n,k] (indices into pred /
  * prob, deg[i] valid entries): pwood_out = median of the neighbours' probabilities (np.median: mean of the two middle
  * values for an even count); label_out: any_wood != 1 -> 1 if any neighbour's prediction > any_wood else 0;
- * any_wood == 1 -> argmax_j sum_{pred == j} prob over j in {0, 1} (first maximum, sums in fp64 like numba's). */
+ * any_wood == 1 -> argmax_j sum_{pred == j} prob over j in {0, 1} (first maximum, sums in fp64 like numba's).
+ * The valid entries of row i are its first min(deg[i], k) slots; the slots behind them are not read.  A row without a valid entry
+ * (deg[i] <= 0) gets label_out = 0, pwood_out = 0.
+ * Status: n == 0 -> P2W_OK (nothing is read); a NULL nbr / deg / pred / prob / label_out / pwood_out -> P2W_ENULL; n < 0, k < 1 or
+ * k > P2W_MAX_K -> P2W_EINVAL. */
 int32_t p2w_vote(const int32_t* nbr, const int32_t* deg, int32_t k, const float* pred, const float* prob, int32_t n,
                  float any_wood, float* label_out, float* pwood_out, p2w_stream_t stream);
 

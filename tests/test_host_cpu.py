@@ -178,7 +178,7 @@ def test_binding_signatures_match_the_header_prototypes():
 def test_header_compiles_as_c_and_the_library_links(tmp_path):
     """include/p2w.h is a C header (no C++ leaks) and libp2w_gfx950.so is an ordinary shared library: a C program built with gcc
     calls the version / error-string / packed-dimension helpers and gets the documented status from every argument error of the
-    small feature and geometry entry points (fake addresses: a status that comes back before the launch needs no GPU) - no Python,
+    small feature and geometry entry points and of the back-projection's (fake addresses: a status that comes back before the launch needs no GPU) - no Python,
     no torch.  The library exports the p2w_* ABI and nothing else."""
     import shutil
     import subprocess
@@ -288,6 +288,52 @@ int main(void) {
     CK(p2w_rowdot(A(F_), 8, 6, A(F_), 0.f, 5, A(float), 0), P2W_EINVAL);
     CK(p2w_rowdot(A(F_), 4, 8, A(F_), 0.f, 5, A(float), 0), P2W_EINVAL);
     CK(p2w_rowdot(A(F_), 8, 8, A(F_), 0.f, -5, A(float), 0), P2W_EINVAL);
+    /* the back-projection's entry points */
+#define D_ const double
+#define K_ const uint64_t
+#define G_ const p2w_grid
+    CK(p2w_vote(0, 0, 64, 0, 0, 0, 1.f, 0, 0, 0), P2W_OK);
+    CK(p2w_vote(0, A(I_), 64, A(F_), A(F_), 5, 1.f, A(float), A(float), 0), P2W_ENULL);
+    CK(p2w_vote(A(I_), 0, 64, A(F_), A(F_), 5, 1.f, A(float), A(float), 0), P2W_ENULL);
+    CK(p2w_vote(A(I_), A(I_), 64, 0, A(F_), 5, 1.f, A(float), A(float), 0), P2W_ENULL);
+    CK(p2w_vote(A(I_), A(I_), 64, A(F_), 0, 5, 1.f, A(float), A(float), 0), P2W_ENULL);
+    CK(p2w_vote(A(I_), A(I_), 64, A(F_), A(F_), 5, 1.f, 0, A(float), 0), P2W_ENULL);
+    CK(p2w_vote(A(I_), A(I_), 64, A(F_), A(F_), 5, 1.f, A(float), 0, 0), P2W_ENULL);
+    CK(p2w_vote(A(I_), A(I_), 0, A(F_), A(F_), 5, 1.f, A(float), A(float), 0), P2W_EINVAL);
+    CK(p2w_vote(A(I_), A(I_), P2W_MAX_K + 1, A(F_), A(F_), 5, 1.f, A(float), A(float), 0), P2W_EINVAL);
+    CK(p2w_vote(A(I_), A(I_), 64, A(F_), A(F_), -5, 1.f, A(float), A(float), 0), P2W_EINVAL);
+    CK(p2w_knn_refine_f64(0, 0, 0, 0, 0, 0, 0., 0., 0., 0, 0, 9, 64, 0, 0, 0), P2W_OK);
+    CK(p2w_knn_refine_f64(0, 0, 0, 0, 0, 0, 0., 0., 0., 0, 5, 0, 64, 0, 0, 0), P2W_OK);
+    CK(p2w_knn_refine_f64(0, A(I_), A(I_), A(K_), A(I_), A(G_), 0., 0., 0., A(D_), 5, 9, 64, A(int32_t), A(int32_t), 0), P2W_ENULL);
+    CK(p2w_knn_refine_f64(A(D_), 0, A(I_), A(K_), A(I_), A(G_), 0., 0., 0., A(D_), 5, 9, 64, A(int32_t), A(int32_t), 0), P2W_ENULL);
+    CK(p2w_knn_refine_f64(A(D_), A(I_), 0, A(K_), A(I_), A(G_), 0., 0., 0., A(D_), 5, 9, 64, A(int32_t), A(int32_t), 0), P2W_ENULL);
+    CK(p2w_knn_refine_f64(A(D_), A(I_), A(I_), 0, A(I_), A(G_), 0., 0., 0., A(D_), 5, 9, 64, A(int32_t), A(int32_t), 0), P2W_ENULL);
+    CK(p2w_knn_refine_f64(A(D_), A(I_), A(I_), A(K_), A(I_), 0, 0., 0., 0., A(D_), 5, 9, 64, A(int32_t), A(int32_t), 0), P2W_ENULL);
+    CK(p2w_knn_refine_f64(A(D_), A(I_), A(I_), A(K_), A(I_), A(G_), 0., 0., 0., 0, 5, 9, 64, A(int32_t), A(int32_t), 0), P2W_ENULL);
+    CK(p2w_knn_refine_f64(A(D_), A(I_), A(I_), A(K_), A(I_), A(G_), 0., 0., 0., A(D_), 5, 9, 64, 0, A(int32_t), 0), P2W_ENULL);
+    CK(p2w_knn_refine_f64(A(D_), A(I_), A(I_), A(K_), A(I_), A(G_), 0., 0., 0., A(D_), 5, 9, 64, A(int32_t), 0, 0), P2W_ENULL);
+    CK(p2w_knn_refine_f64(A(D_), A(I_), A(I_), A(K_), A(I_), A(G_), 0., 0., 0., A(D_), 5, 9, 0, A(int32_t), A(int32_t), 0), P2W_EINVAL);
+    CK(p2w_knn_refine_f64(A(D_), A(I_), A(I_), A(K_), A(I_), A(G_), 0., 0., 0., A(D_), 5, 9, P2W_MAX_K + 1, A(int32_t), A(int32_t), 0), P2W_EINVAL);
+    CK(p2w_knn_refine_f64(A(D_), A(I_), A(I_), A(K_), A(I_), A(G_), 0., 0., 0., A(D_), -5, 9, 64, A(int32_t), A(int32_t), 0), P2W_EINVAL);
+    CK(p2w_knn_refine_f64(A(D_), A(I_), A(I_), A(K_), A(I_), A(G_), 0., 0., 0., A(D_), 5, -9, 64, A(int32_t), A(int32_t), 0), P2W_EINVAL);
+    CK(p2w_morton_order(0, 0, 0, 0, 0, 0, 0), P2W_OK);
+    CK(p2w_morton_order(0, 5, A(G_), A(int32_t), A(void), 1 << 20, 0), P2W_ENULL);
+    CK(p2w_morton_order(A(F_), 5, 0, A(int32_t), A(void), 1 << 20, 0), P2W_ENULL);
+    CK(p2w_morton_order(A(F_), 5, A(G_), 0, A(void), 1 << 20, 0), P2W_ENULL);
+    CK(p2w_morton_order(A(F_), 5, A(G_), A(int32_t), 0, 1 << 20, 0), P2W_ENULL);
+    CK(p2w_morton_order(U(F_), 5, A(G_), A(int32_t), A(void), 1 << 20, 0), P2W_EALIGN);
+    CK(p2w_morton_order(A(F_), 5, A(G_), A(int32_t), U(void), 1 << 20, 0), P2W_EALIGN);
+    CK(p2w_morton_order(A(F_), -5, A(G_), A(int32_t), A(void), 1 << 20, 0), P2W_EINVAL);
+    CK(p2w_morton_order(A(F_), 5, A(G_), A(int32_t), A(void), 0, 0), P2W_EWORKSPACE);
+    CK(p2w_morton_order(A(F_), 5, A(G_), A(int32_t), A(void), p2w_morton_order_ws_bytes(5) - 1, 0), P2W_EWORKSPACE);
+    CK(p2w_cell_starts(A(K_), 5, 10, 0, A(void), 1 << 20, 0), P2W_ENULL);
+    CK(p2w_cell_starts(A(K_), 5, 10, A(int32_t), 0, 1 << 20, 0), P2W_ENULL);
+    CK(p2w_cell_starts(A(K_), 5, 10, A(int32_t), U(void), 1 << 20, 0), P2W_EALIGN);
+    CK(p2w_cell_starts(A(K_), -5, 10, A(int32_t), A(void), 1 << 20, 0), P2W_EINVAL);
+    CK(p2w_cell_starts(A(K_), 5, -10, A(int32_t), A(void), 1 << 20, 0), P2W_EINVAL);
+    CK(p2w_cell_starts(A(K_), 5, INT32_MAX, A(int32_t), A(void), 1 << 20, 0), P2W_EINVAL);
+    CK(p2w_cell_starts(A(K_), 5, 10, A(int32_t), A(void), 0, 0), P2W_EWORKSPACE);
+    CK(p2w_cell_starts(A(K_), 5, 10, A(int32_t), A(void), p2w_cell_starts_ws_bytes(10) - 1, 0), P2W_EWORKSPACE);
     printf("abi ok %d %zu\\n", (int)p2w_version(), sizeof(p2w_epilogue));
     return 0;
 }
