@@ -263,10 +263,15 @@ int32_t p2w_knn_refine_f64(const double* cand_sorted, const int32_t* cand_index,
  *      index), keys_sorted[n] / grid = its sorted_keys_out / grid_out, cell_start = an optional p2w_cell_starts table of those keys
  *      (NULL: runs are found by bisection).  The grid's cell must be at least the tolerance plus the fp32 rounding of the local
  *      coordinates and of the key division (pointstowood_amd/cluster.py: safe_cell), so that every joined pair lies in adjacent cells.
+ *      Any cell at or above it gives the same labels; a grid may be one cell thick on any axis, or one cell in all.
  * Out: labels_out[n] int64; counts_out[2] (device) = {number of kept clusters, number of points labelled -1}; pairs_out (optional,
- *      device uint64) = the number of point pairs whose distance the link stage measured.
+ *      device uint64) = the number of point pairs whose distance the link stage measured = the number of unordered pairs of distinct
+ *      points whose cells are equal or differ by at most 1 on every axis, each pair once (it depends on the grid, not on the tolerance).
  * `stages`: P2W_CLUSTER_ALL, or the stages one at a time in order (link, compress, number) on the same ws - the per-stage timing of
- * tools/cluster_bench.py.  n < 2^31 - 1, tolerance finite and >= 0 (P2W_EINVAL otherwise).
+ * tools/cluster_bench.py: the link stage writes pairs_out, the number stage labels_out and counts_out, and the outputs equal those of
+ * P2W_CLUSTER_ALL.  Neither ws nor an output needs any initial content; a repeated call gives the same bits.
+ * n == 0 -> P2W_OK: counts_out = {0, 0}, pairs_out = 0, labels_out is not written (the pointers of the requested stages are still
+ * checked).  n < 2^31 - 1, tolerance finite and >= 0 (P2W_EINVAL otherwise).
  * ws: 16-byte aligned, p2w_euclid_cluster_ws_bytes(n) bytes. */
 #define P2W_CLUSTER_LINK 1     /* union-find over the grid: every pair of adjacent cells measured once, the larger root hooked under the smaller */
 #define P2W_CLUSTER_COMPRESS 2 /* every point's root (= its component's smallest index) and the component sizes */
