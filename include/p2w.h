@@ -61,7 +61,10 @@ int32_t p2w_pack_xyzr(const float* pos, int32_t pos_stride, const float* refl, c
  *      occupied cell, ascending cell id i.e. voxel-major), ptr_out[B+1] (CSR of the sampled level;
  *      ptr_out[B] = M), batch_out[M]; order_out[n] (optional, may be NULL) = the input point indices in
  *      ascending (voxel, cell id) order - a spatially coherent visiting order for the searches below.
- * ws : p2w_voxel_sample_ws_bytes(n_bound) bytes of scratch. */
+ * ws : p2w_voxel_sample_ws_bytes(n_bound) bytes of scratch.
+ * Neither the outputs nor ws need any initial content (p2w_voxel_sample, p2w_voxel_sample_table, p2w_voxel_grid,
+ * p2w_consecutive_cluster alike; only p2w_voxel_sample_table_prepared expects the state p2w_voxel_sample_table_prepare leaves);
+ * entries behind the written counts (idx_out[M..], inv_out[n..], cell_start_out[cells + 1 ..] ...) are left as they were. */
 /* Geometry of the cell grid a sampling call used (device-resident, written by p2w_voxel_sample): cell (cx, cy, cz)
  * of voxel b has key ((( (b - b_lo) * dims[2] + cz) * dims[1] + cy) * dims[0] + cx. */
 typedef struct p2w_grid {
@@ -134,7 +137,10 @@ int32_t p2w_level_gather(const float* xyzr_src, const int32_t* idx, const int32_
  * Queries are x[qidx[q]] (qidx NULL = identity).  For query q of voxel b the `cap` candidates of lowest index among
  * those of ptr_x[b]..ptr_x[b+1] with d2 < (float)(r*r) (r is a double, as torch-cluster's host code takes it) are
  * written in ascending index order to nbr[q*cap + 0..deg[q]-1]; remaining slots are -1.  tile_bbox: optional, see
- * p2w_tile_bbox. */
+ * p2w_tile_bbox.
+ * NaN (p2w_ball_query and p2w_knn): a candidate with a NaN coordinate is never reported, deg counts only admitted candidates
+ * (p2w_knn: min(k, candidates without NaN)), and every other query's row is what it would be without that candidate; a query
+ * with a NaN coordinate gets deg 0. */
 int32_t p2w_ball_query(const float* xyzr_x, const int32_t* ptr_x, const float* xyzr_q, const int32_t* qidx,
                        const int32_t* ptr_q, int32_t B, int32_t m_bound, double r, int32_t cap, int32_t* nbr,
                        int32_t* deg, const float* tile_bbox, int32_t flags, p2w_stream_t stream);
@@ -158,7 +164,10 @@ int32_t p2w_knn_grid(const float* xyzr_x, const uint64_t* keys_x, const int32_t*
  * bound is verified (k candidates must turn up inside it), a wrong one only costs a rescan.  p2w_knn_hint2 derives
  * bounds for k <= 2 when the candidates are the sampled level of the queries' level (the interpolation searches):
  * rank[i] = index of query i's cell representative among the candidates (p2w_voxel_sample's inv_out, or
- * rank_sorted_out when the queries are given in sorted order). */
+ * rank_sorted_out when the queries are given in sorted order).
+ * The rule: hint[i] = max(d2 to the own representative xyzr_c[rank[i]], smallest d2 to the representatives rank[i +- s], s = 1 .. 8,
+ * that differ from the own one - positions inside query i's own voxel only, no further s once one has been seen and s >= 2),
+ * +inf when no second representative turns up (a voxel of one point or of one cell). */
 int32_t p2w_knn_hint2(const float* xyzr_q, const int32_t* rank, const int32_t* ptr_q, int32_t B, int32_t m_bound,
                       const float* xyzr_c, float* hint, p2w_stream_t stream);
 int32_t p2w_ball_query_grid(const float* xyzr_x, const uint64_t* keys_x, const int32_t* ptr_x, const p2w_grid* grid,
