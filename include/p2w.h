@@ -215,20 +215,33 @@ int32_t p2w_morton_order(const float* xyzr, int32_t n, const p2w_grid* grid, int
  * stride_d with the column minima lo_d and the running products of the per-column cell counts as strides (fp32 subtract /
  * divide / truncate, int64 result).  A row with a non-finite value takes no part in the minima / maxima and gets the key
  * P2W_CELL_NONFINITE (sorts last; the reference's own result on such input is the cast of a NaN, i.e. undefined).
- * ws: >= 256 bytes. */
+ * Only columns 0 .. D-1 of a row are read: with ld > D the pad columns may hold anything, NaN included.  P is not modified, exactly
+ * cell_out[0 .. n) is written, and neither cell_out nor ws needs initial content.  ws: >= 256 bytes.
+ * Status, in this order: n == 0 -> P2W_OK (nothing is read or written); a NULL P / cell_out / ws -> P2W_ENULL; n < 0, D < 1, D > 16,
+ * ld < D or a size that is not > 0 (0, negative, NaN) -> P2W_EINVAL; ws_bytes too small -> P2W_EWORKSPACE. */
 #define P2W_CELL_NONFINITE INT64_MAX
 int32_t p2w_cells_nd(const float* P, int32_t n, int32_t D, int32_t ld, float size, int64_t* cell_out, void* ws, size_t ws_bytes,
                      p2w_stream_t stream);
 /* STABLE ascending sort of n (64-bit key, int32 value) pairs - hand-written LSD radix sort, 8-bit digits, as many passes as the
  * largest key has bytes (decided on the device).  vals_in NULL: values = 0..n-1, i.e. vals_out = the stable argsort the
- * voxeliser needs (points of a voxel keep their order, as the reference's nonzero() scan gives them).  In and out buffers must
- * differ.  ws: 16-byte aligned, p2w_sort_pairs_u64_ws_bytes(n) bytes. */
+ * voxeliser needs (points of a voxel keep their order, as the reference's nonzero() scan gives them).  Keys compare as
+ * UNSIGNED 64-bit integers (a key with bit 63 set sorts behind every key without).  In and out buffers must differ; keys_in and
+ * vals_in are not modified, exactly keys_out / vals_out[0 .. n) are written, and neither the outputs nor ws need initial content
+ * (the same ws may serve call after call).  ws: 16-byte aligned, p2w_sort_pairs_u64_ws_bytes(n) bytes.
+ * Status, in this order: n == 0 -> P2W_OK (nothing is read or written); a NULL keys_in / keys_out / vals_out / ws -> P2W_ENULL; ws
+ * not 16-byte aligned -> P2W_EALIGN; n < 0, keys_in == keys_out or a non-NULL vals_in == vals_out -> P2W_EINVAL; ws_bytes too small
+ * -> P2W_EWORKSPACE. */
 size_t p2w_sort_pairs_u64_ws_bytes(int32_t n);
 int32_t p2w_sort_pairs_u64(const uint64_t* keys_in, uint64_t* keys_out, const int32_t* vals_in, int32_t* vals_out, int32_t n, void* ws,
                            size_t ws_bytes, p2w_stream_t stream);
 /* Runs of equal keys in a SORTED key array that hold at least min_count elements (the voxeliser's min_pts filter,
  * preprocessing.py:60-62): starts_out / counts_out[0 .. *n_out) in ascending order (buffers of n entries), *n_out on the device.
- * ws: 16-byte aligned, p2w_key_runs_ws_bytes(n) bytes. */
+ * Keys are compared for equality only (any 64-bit pattern).  A run is kept when count >= min_count, so min_count <= 0 keeps every
+ * run like min_count == 1.  keys_sorted is not modified, starts_out / counts_out from *n_out on are left as they were, and neither
+ * the outputs nor ws need initial content.  ws: 16-byte aligned, p2w_key_runs_ws_bytes(n) bytes.
+ * Status, in this order: a NULL n_out -> P2W_ENULL; n == 0 -> *n_out = 0 is enqueued, nothing else is read or written, P2W_OK; a
+ * NULL keys_sorted / starts_out / counts_out / ws -> P2W_ENULL; ws not 16-byte aligned -> P2W_EALIGN; n < 0 -> P2W_EINVAL; ws_bytes
+ * too small -> P2W_EWORKSPACE. */
 size_t p2w_key_runs_ws_bytes(int32_t n);
 int32_t p2w_key_runs(const uint64_t* keys_sorted, int32_t n, int32_t min_count, int32_t* starts_out, int32_t* counts_out, int32_t* n_out,
                      void* ws, size_t ws_bytes, p2w_stream_t stream);

@@ -1,7 +1,7 @@
 // Device-wide primitives of the geometry / plot-level kernels, hand-written for gfx950 (wave64): a STABLE least-significant-
 // digit radix sort of (64-bit key, 32-bit value) pairs and an exclusive scan of int32.  They replace rocPRIM in the sort
 // sampler (p2w_voxel_sample / p2w_consecutive_cluster), the Morton ordering of the back-projection (p2w_morton_order) and
-// the voxeliser (p2w_sort_pairs_u64, p2w_voxel_runs).
+// the voxeliser (p2w_sort_pairs_u64, p2w_key_runs).
 //
 // Radix sort: 8-bit digits, one pass = histogram (per 4096-key tile) -> scan of the [digit][tile] table -> stable scatter.
 //   * the number of passes follows the DATA: an OR over the keys gives the highest set bit, passes above it return at once

@@ -18,7 +18,8 @@ def _L():
 
 @pytest.mark.parametrize("n,bits,with_vals", [(1, 64, False), (63, 8, True), (4096, 16, False), (4097, 20, True), (100003, 37, False),
                                               (1 << 20, 63, True), (300000, 0, False), (70000, 9, True),
-                                              # beyond 1 048 576 keys the histogram scan is two-level (rs_scan_tile / _sums / _add): ADVICE r4
+                                              # beyond 131 072 keys (RS_SCAN_ONE = 8192 table entries = 32 tiles) the histogram scan is two-level
+                                              # (rs_scan_tile / _sums / _add): ADVICE r4; tests/test_gpu_prim_kernels.py runs both sides of that size
                                               ((1 << 20) + 1, 40, False), (5_000_011, 24, True), (5_000_011, 45, False)])
 def test_radix_sort_pairs_is_a_stable_sort(n, bits, with_vals):
     """p2w_sort_pairs_u64 == torch.sort(stable=True): keys of 0..63 significant bits (the pass count follows the data), many

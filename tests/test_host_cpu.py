@@ -178,7 +178,7 @@ def test_binding_signatures_match_the_header_prototypes():
 def test_header_compiles_as_c_and_the_library_links(tmp_path):
     """include/p2w.h is a C header (no C++ leaks) and libp2w_gfx950.so is an ordinary shared library: a C program built with gcc
     calls the version / error-string / packed-dimension helpers and gets the documented status from every argument error of the
-    small feature and geometry entry points and of the back-projection's (fake addresses: a status that comes back before the launch needs no GPU) - no Python,
+    small feature and geometry entry points, of the back-projection's and of the voxeliser's primitives (fake addresses: a status that comes back before the launch needs no GPU) - no Python,
     no torch.  The library exports the p2w_* ABI and nothing else."""
     import shutil
     import subprocess
@@ -188,6 +188,7 @@ def test_header_compiles_as_c_and_the_library_links(tmp_path):
         pytest.skip("no gcc")
     src = tmp_path / "abi.c"
     src.write_text('''
+#include <math.h>
 #include <stdio.h>
 #include <string.h>
 #include "p2w.h"
@@ -334,6 +335,46 @@ int main(void) {
     CK(p2w_cell_starts(A(K_), 5, INT32_MAX, A(int32_t), A(void), 1 << 20, 0), P2W_EINVAL);
     CK(p2w_cell_starts(A(K_), 5, 10, A(int32_t), A(void), 0, 0), P2W_EWORKSPACE);
     CK(p2w_cell_starts(A(K_), 5, 10, A(int32_t), A(void), p2w_cell_starts_ws_bytes(10) - 1, 0), P2W_EWORKSPACE);
+    /* the voxeliser's primitives: every status below comes back before any HIP call (p2w_key_runs with n == 0 and a count to write
+     * enqueues a memset and stays out).  B = a second aligned address: in and out buffers must differ. */
+#define B(T) ((T*)32)
+    CK(p2w_cells_nd(0, 0, 3, 3, 1.f, 0, 0, 0, 0), P2W_OK);
+    CK(p2w_cells_nd(0, 5, 3, 3, 1.f, A(int64_t), A(void), 256, 0), P2W_ENULL);
+    CK(p2w_cells_nd(A(F_), 5, 3, 3, 1.f, 0, A(void), 256, 0), P2W_ENULL);
+    CK(p2w_cells_nd(A(F_), 5, 3, 3, 1.f, A(int64_t), 0, 256, 0), P2W_ENULL);
+    CK(p2w_cells_nd(A(F_), -5, 3, 3, 1.f, A(int64_t), A(void), 256, 0), P2W_EINVAL);
+    CK(p2w_cells_nd(A(F_), 5, 0, 3, 1.f, A(int64_t), A(void), 256, 0), P2W_EINVAL);
+    CK(p2w_cells_nd(A(F_), 5, 17, 17, 1.f, A(int64_t), A(void), 256, 0), P2W_EINVAL);
+    CK(p2w_cells_nd(A(F_), 5, 3, 2, 1.f, A(int64_t), A(void), 256, 0), P2W_EINVAL);
+    CK(p2w_cells_nd(A(F_), 5, 3, 3, 0.f, A(int64_t), A(void), 256, 0), P2W_EINVAL);
+    CK(p2w_cells_nd(A(F_), 5, 3, 3, -1.f, A(int64_t), A(void), 256, 0), P2W_EINVAL);
+    CK(p2w_cells_nd(A(F_), 5, 3, 3, NAN, A(int64_t), A(void), 256, 0), P2W_EINVAL);
+    CK(p2w_cells_nd(A(F_), 5, 3, 3, 1.f, A(int64_t), A(void), 64, 0), P2W_EWORKSPACE);
+    CK(p2w_cells_nd(A(F_), 5, 0, 3, 1.f, A(int64_t), A(void), 64, 0), P2W_EINVAL);        /* the sizes before the workspace */
+    CK(p2w_sort_pairs_u64(0, 0, 0, 0, 0, 0, 0, 0), P2W_OK);
+    CK(p2w_sort_pairs_u64(0, B(uint64_t), A(I_), B(int32_t), 5, A(void), 1 << 20, 0), P2W_ENULL);
+    CK(p2w_sort_pairs_u64(A(K_), 0, A(I_), B(int32_t), 5, A(void), 1 << 20, 0), P2W_ENULL);
+    CK(p2w_sort_pairs_u64(A(K_), B(uint64_t), A(I_), 0, 5, A(void), 1 << 20, 0), P2W_ENULL);
+    CK(p2w_sort_pairs_u64(A(K_), B(uint64_t), A(I_), B(int32_t), 5, 0, 1 << 20, 0), P2W_ENULL);
+    CK(p2w_sort_pairs_u64(A(K_), B(uint64_t), A(I_), B(int32_t), 5, U(void), 1 << 20, 0), P2W_EALIGN);
+    CK(p2w_sort_pairs_u64(A(K_), B(uint64_t), A(I_), B(int32_t), -5, A(void), 1 << 20, 0), P2W_EINVAL);
+    CK(p2w_sort_pairs_u64(A(K_), A(uint64_t), A(I_), B(int32_t), 5, A(void), 1 << 20, 0), P2W_EINVAL);       /* keys in place */
+    CK(p2w_sort_pairs_u64(A(K_), B(uint64_t), A(I_), A(int32_t), 5, A(void), 1 << 20, 0), P2W_EINVAL);       /* values in place */
+    CK(p2w_sort_pairs_u64(A(K_), A(uint64_t), 0, B(int32_t), 5, U(void), 0, 0), P2W_EALIGN);                 /* alignment first */
+    CK(p2w_sort_pairs_u64(A(K_), A(uint64_t), 0, B(int32_t), 5, A(void), 0, 0), P2W_EINVAL);                 /* then the scalars */
+    CK(p2w_sort_pairs_u64(A(K_), B(uint64_t), 0, B(int32_t), 5, A(void), 0, 0), P2W_EWORKSPACE);
+    CK(p2w_sort_pairs_u64(A(K_), B(uint64_t), A(I_), B(int32_t), 5, A(void), p2w_sort_pairs_u64_ws_bytes(5) - 1, 0), P2W_EWORKSPACE);
+    CK(p2w_key_runs(A(K_), 5, 1, A(int32_t), B(int32_t), 0, A(void), 1 << 20, 0), P2W_ENULL);
+    CK(p2w_key_runs(0, 0, 1, 0, 0, 0, 0, 0, 0), P2W_ENULL);                                /* no count to write, even for n == 0 */
+    CK(p2w_key_runs(0, 5, 1, A(int32_t), B(int32_t), A(int32_t), A(void), 1 << 20, 0), P2W_ENULL);
+    CK(p2w_key_runs(A(K_), 5, 1, 0, B(int32_t), A(int32_t), A(void), 1 << 20, 0), P2W_ENULL);
+    CK(p2w_key_runs(A(K_), 5, 1, A(int32_t), 0, A(int32_t), A(void), 1 << 20, 0), P2W_ENULL);
+    CK(p2w_key_runs(A(K_), 5, 1, A(int32_t), B(int32_t), A(int32_t), 0, 1 << 20, 0), P2W_ENULL);
+    CK(p2w_key_runs(A(K_), 5, 1, A(int32_t), B(int32_t), A(int32_t), U(void), 1 << 20, 0), P2W_EALIGN);
+    CK(p2w_key_runs(A(K_), -5, 1, A(int32_t), B(int32_t), A(int32_t), A(void), 1 << 20, 0), P2W_EINVAL);
+    CK(p2w_key_runs(A(K_), -5, 1, A(int32_t), B(int32_t), A(int32_t), U(void), 1 << 20, 0), P2W_EALIGN);     /* alignment first */
+    CK(p2w_key_runs(A(K_), 5, 1, A(int32_t), B(int32_t), A(int32_t), A(void), 0, 0), P2W_EWORKSPACE);
+    CK(p2w_key_runs(A(K_), 5, 1, A(int32_t), B(int32_t), A(int32_t), A(void), p2w_key_runs_ws_bytes(5) - 1, 0), P2W_EWORKSPACE);
     printf("abi ok %d %zu\\n", (int)p2w_version(), sizeof(p2w_epilogue));
     return 0;
 }
